@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: navigation-steps/sec (whole job) of the NaviLLM training hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`value`, `ms_per_step` = the timed window / K).
+--full adds everything else the line has carried: GEMM event timing + roofline, the DP exchange profile, the whole-episode and
+other-mode windows, forward-only inference, the CPU baseline and the config-3/4/5 extras (--no-* options below thin it out).
+--dump-outputs DIR writes what the last timed step computed (same seeds, same inputs on every run) as DIR/<name>.npy.
 
 One "step" = one iteration of the rollout loop (tasks/agents/mp3d_agent.py:660) for the rank's batch of
 B=8 synthetic R2R-shaped episodes: model('panorama') + model('navigation') + action CE + full
@@ -53,9 +58,20 @@ def parse():
                     help="how the training step treats the prompt's static prefix (instruction + template, ~530 of ~650 tokens): "
                          "prefix_reuse (default) = forward once per episode, K/V reused by every step, one deferred prefix backward "
                          "(navillm_amd/episode.py; gradients pinned to the reference by fixture G12); recompute = the whole prompt "
-                         "through the LM at every step like the reference's rollout.  The other mode is measured too and reported "
-                         "under `other_mode`.")
-    return ap.parse_args()
+                         "through the LM at every step like the reference's rollout.  With --full the other mode is measured too and "
+                         "reported under `other_mode`.")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: GEMM event timing and roofline, the DP exchange profile, the "
+                         "whole-episode and other-mode windows, forward-only inference, the CPU baseline and the config-3/4/5 extras.  "
+                         "Without it the run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy (float32): its loss, its "
+                         "fuse_logits (masked slots as 0, with fuse_logits_valid marking the real ones) and a fixed seeded sample of "
+                         "every parameter group after the step's optimizer update")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_cfg(a):
@@ -753,6 +769,38 @@ def cpu_baseline(a, cfg, seed):
                       f"torch CPU bf16, {cores} threads = the CPUs this container may use (cpu_count {os.cpu_count()}, cgroup quota applied)"}
 
 
+DUMP_SAMPLE = 1 << 20           # parameters per group written by --dump-outputs (4 MB each as float32)
+
+
+def dump_outputs(path, loss, logits, store):
+    """--dump-outputs: the last timed step's loss and fuse_logits (resolved from their deferred handles: the episode is over by now) and
+    the parameters after its optimizer update, one fixed sample of DUMP_SAMPLE positions per flat group (seeded, sorted).
+    The logits carry -inf in the map slots the step may not choose (padding, the masked candidates): they are written as
+    `fuse_logits` with those slots set to 0 plus `fuse_logits_valid` (1 = a real logit, 0 = masked), so every array is finite
+    unless the step computed a NaN or +inf, which is written as it is."""
+    import numpy as np
+
+    def host(x):
+        if not torch.is_tensor(x) and hasattr(x, "value"):
+            x = x.value
+        if torch.is_tensor(x):
+            return x.detach().float().cpu().numpy()
+        return np.asarray(x, dtype=np.float32)
+
+    os.makedirs(path, exist_ok=True)
+    lg = host(logits)
+    valid = lg != -np.inf
+    out = {"loss": host(loss).reshape(1), "fuse_logits": np.where(valid, lg, 0.0), "fuse_logits_valid": valid}
+    for g in sorted(store.param):
+        p = store.param[g]
+        n = p.numel()
+        idx = np.unique(np.random.default_rng(0).integers(0, n, size=DUMP_SAMPLE)) if n > DUMP_SAMPLE else np.arange(n)
+        out[f"params_{g}_sample"] = p[torch.from_numpy(idx).to(p.device)].float().cpu().numpy()
+    for name, arr in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr.astype(np.float32))
+    return sorted(out)
+
+
 def relaunch_one_rank_per_gpu(a):
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks ourselves (one process per GPU, exactly the
     launch line of the module docstring) and hand their output through.  Never falls back to a single GPU."""
@@ -888,6 +936,7 @@ def main():
     crit = CrossEntropyLoss()
     ep = SyntheticEpisodes(cfg, a.batch, seed=seed, instr_len=a.instr_len, device=device)
     import contextlib
+    last_logits = [None]                # fuse_logits of the latest step (--dump-outputs)
 
     def make_step(mode):
         prefix = mode == "prefix_reuse"
@@ -911,6 +960,7 @@ def main():
                 # steps' LM forward is batched into finish_episode() as well (round 4; --no-tf-batch: per-step forward as in round 3)
                 model.begin_episode(ep.prefix_ids(), teacher_forced=TF_BATCH)
             loss, logits = nav_step(wrapped, crit, ep, train=True, last=last, final=last and not prefix)
+            last_logits[0] = logits
             if last:
                 if explicit:
                     with dp_ctx():                            # the LAST backward before the optimizer step: DP exchanges from inside it
@@ -954,7 +1004,8 @@ def main():
         if getattr(wrapped, "profile", False):
             wrapped.exchange_stats(reset=True)      # the exchange events of the setup / warmup steps (first one: RCCL channel setup) do not count
         tm = GemmTimer()
-        if not a.no_profile:
+        profile = a.full and not a.no_profile
+        if profile:
             tm.install(ops)
         torch.cuda.synchronize()
         if world > 1 and sync_ranks:
@@ -970,7 +1021,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        if not a.no_profile:
+        if profile:
             tm.uninstall()
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if (REHEARSAL or not dist.is_initialized() or dist.get_backend() == "gloo") else device)
         if world > 1 and sync_ranks:
@@ -987,11 +1038,14 @@ def main():
             model.grad_handover("bench") if getattr(model, "_auto_open", False) else None
             model.auto_episode = False
 
-    if world > 1 and hasattr(wrapped, "exchange_stats"):
+    if world > 1 and hasattr(wrapped, "exchange_stats") and a.full:
         wrapped.profile = True           # HIP events around the exchange of every optimizer step (side stream + the join): `dp.exchange`
     dt, timer, loss = run_mode(a.mode, a.steps, a.warmup, a.prewarm, True)
     seq_len_main = int(max(ep.S_hist)) if ep.S_hist else None
     main_stats = dict(model.episode.stats) if (a.mode == "prefix_reuse" and model.episode is not None) else None
+    if a.dump_outputs and rank == 0:
+        phase(f"outputs written to {a.dump_outputs}: {', '.join(dump_outputs(a.dump_outputs, loss, last_logits[0], model.store))}")
+    last_logits[0] = None
 
     # ---- N > 1: what the gradient exchange cost inside the timed region, and which RCCL every rank bound
     dp_exchange, rccl_versions = None, None
@@ -1009,7 +1063,7 @@ def main():
     # ---- the same mode over WHOLE 6-step episodes (steady state; reported aside, never `value`): the K-step window above ends with a
     # short episode whenever K is not a multiple of 6
     whole = None
-    if a.steps % STEPS_PER_EPISODE and (not a.no_extras or a.model != "tiny") and not a.no_other_mode:
+    if a.full and a.steps % STEPS_PER_EPISODE and (not a.no_extras or a.model != "tiny") and not a.no_other_mode:
         try:
             w_steps = 3 * STEPS_PER_EPISODE
             w_dt, _, _ = run_mode(a.mode, w_steps, 0, 0, world > 1)
@@ -1037,7 +1091,7 @@ def main():
             whole = {"error": f"{type(e).__name__}: {e}"}
     # ---- the OTHER training mode, same process, same model (reported under `other_mode`, never `value`)
     other = None
-    if (not a.no_extras or a.model != "tiny") and not a.no_other_mode:
+    if a.full and (not a.no_extras or a.model != "tiny") and not a.no_other_mode:
         other_mode = "recompute" if a.mode == "prefix_reuse" else "prefix_reuse"
         try:
             o_steps = 2 * STEPS_PER_EPISODE
@@ -1054,7 +1108,7 @@ def main():
         ep.reset()
     # ---- untimed extra: the same nav step without loss/backward (validation rollout, mp3d_agent.py:530-590)
     infer = infer_kv = None
-    if a.infer_steps > 0:
+    if a.full and a.infer_steps > 0:
         try:        # extras must never take the headline number down with them (nor leave a rank behind at the final barrier)
             infer, infer_kv = inference_extras(a, model, wrapped, crit, ep)
         except Exception as e:
@@ -1063,7 +1117,7 @@ def main():
         model.kv = None
         model.train()
     cpu_line = None
-    if rank == 0 and not a.no_cpu_baseline and world == 1:
+    if a.full and rank == 0 and not a.no_cpu_baseline and world == 1:
         phase("cpu baseline")
         try:
             cpu_line = cpu_baseline(a, cfg, 1234)
@@ -1072,7 +1126,7 @@ def main():
                         "sample": f"failed: {type(e).__name__}: {e}"}
         torch.set_num_threads(max(1, min(16, usable_cpus() // max(world, 1))))
     extras = {}
-    if not a.no_extras and (a.model != "tiny" or a.extras_on_tiny):
+    if a.full and not a.no_extras and (a.model != "tiny" or a.extras_on_tiny):
         for name, fn in (("mixed_task_training_config3", lambda: mixed_task_extra(a, cfg, model, wrapped, opt, crit, device, seed + 100)),
                          ("long_horizon_config4", lambda: long_horizon_extra(a, cfg, model, wrapped, crit, device, seed + 200)),
                          ("reference_launch_line", lambda: reference_launch_extra(a, cfg, model, opt, crit, device, seed + 400) if world == 1 else None),
@@ -1143,7 +1197,7 @@ def main():
         if infer_kv is not None:
             line["inference_prefix_kv_reuse"] = infer_kv
         line.update(extras)
-        rl = roofline_of(timer, dt, a.steps, a.mode, model)
+        rl = roofline_of(timer, dt, a.steps, a.mode, model) if a.full else None
         if rl is not None:
             line["roofline"] = rl
         if cpu_line is not None:

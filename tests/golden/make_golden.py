@@ -236,9 +236,27 @@ def npf(t):
     return np.asarray(t)
 
 
+PART_BYTES = 960 * 1024        # committed files stay below 1 MiB: a larger fixture is split into NAME.npz, NAME.part1.npz, ... (tests/util.gold)
+
+
 def save(name, **arrs):
     path = os.path.join(HERE, name)
     np.savez_compressed(path, **{k: npf(v) for k, v in arrs.items()})
+    if os.path.getsize(path) > PART_BYTES:
+        import zipfile
+        with zipfile.ZipFile(path) as z:
+            members = [(i.filename, z.read(i.filename), i.compress_size) for i in z.infolist()]
+        parts, size = [[]], 0
+        for m in members:
+            if parts[-1] and size + m[2] > PART_BYTES:
+                parts.append([])
+                size = 0
+            parts[-1].append(m)
+            size += m[2]
+        for i, part in enumerate(parts):
+            with zipfile.ZipFile(path if i == 0 else os.path.join(HERE, f"{name[:-4]}.part{i}.npz"), "w", zipfile.ZIP_DEFLATED) as w:
+                for fn, data, _ in part:
+                    w.writestr(fn, data)
     print(f"  wrote {name}: {os.path.getsize(path)/1024:.1f} KiB")
 
 

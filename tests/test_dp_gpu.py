@@ -286,7 +286,7 @@ def test_two_rank_rehearsal_on_one_gpu_prints_one_n2_line():
     env = dict(os.environ, NAVILLM_BENCH_REHEARSAL="1", NAVILLM_BUILD_REUSE="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--model", "tiny", "--steps", "7", "--warmup", "1",
-                        "--prewarm", "1", "--instr-len", "40", "--batch", "2", "--no-cpu-baseline", "--infer-steps", "0"],
+                        "--prewarm", "1", "--instr-len", "40", "--batch", "2", "--no-cpu-baseline", "--infer-steps", "0", "--full"],
                        capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

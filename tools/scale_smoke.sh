@@ -14,7 +14,7 @@ if [ "$HAVE" -lt "$N" ]; then
     echo "scale_smoke: $HAVE GPU(s) visible, $N needed -- nothing run"; exit 3
 fi
 mkdir -p gpurun_out
-timeout 900 python bench.py --gpus "$N" --model tiny --steps 12 --warmup 6 --no-cpu-baseline --infer-steps 0 \
+timeout 900 python bench.py --gpus "$N" --model tiny --steps 12 --warmup 6 --no-cpu-baseline --infer-steps 0 --full \
     > gpurun_out/scale_smoke_n$N.json 2> gpurun_out/scale_smoke_n$N.err
 rc=$?
 echo "bench rc=$rc"
