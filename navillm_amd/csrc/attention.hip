@@ -17,7 +17,6 @@
 //  * lse is kept in the log2 domain (lse2 = m2 + log2(l)); fully masked rows store +inf so
 //    the backward's exp2(s2 - lse2) is exactly 0 for them.
 #include "nv_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -151,8 +150,8 @@ struct AttnArgs {
     float scale;           // head_dim^-0.5
     const bf16_t* rope_cos; const bf16_t* rope_sin;   // backward only, optional: apply RoPE^T to dQ/dK as they are written
     float* kvacc;          // backward over a K/V cache, optional (navillm_amd/episode.py): fp32 [rows, 2*H*HD] accumulator of the gradients the
-    const int* kvacc_len;  // steps of an episode send into the cached PREFIX rows: key rows < kvacc_len[b] of sample b add (kvacc_first:
-    int kvacc_first;       // store) their dK | dV there straight from the fp32 MFMA accumulators and write no bf16 row
+    const int* kvacc_len;  // steps of an episode send into the cached PREFIX rows: key rows < kvacc_len[b] of sample b store (kvacc_add:
+    int kvacc_add;         // add) their dK | dV there straight from the fp32 MFMA accumulators and write no bf16 row
     int stat_cap;          // backward dK/dV: > 0 = the sample's lse / dsum rows are copied to LDS once per block (stat_cap floats each, a
                            // multiple of 32 >= S) and read from there; 0 = loaded from HBM inside the tile loop (S too long for the LDS budget)
     const int* dyn;        // forward over a K/V cache, optional: {S, q_row_min} read from DEVICE memory (a decode step replayed from a
@@ -258,7 +257,106 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_
 }
 
 // =========================================================================== forward
-// grid (ceil(S/128), B*H), 256 threads: wave w owns queries q0 + w*32 .. +31 (two 16-query tiles)
+// The tile step of both forward kernels (attn_fwd_kernel, epi_fwd_kernel): one 64-key tile (K at sk, V at sv) against a wave's two
+// 16-query tiles qf.  A lane holds query lane&15 of tile j and the tile keys i*16 + g*4 + r (g = lane>>4); key0 = the tile's first
+// key in the caller's numbering, key_ok(key, j) = may query tile j of this lane see that key.  interior (wave-uniform): no pair of
+// the tile is masked, and key_ok is not evaluated -- most tiles of a long prompt.
+
+// S^T = K Q^T : 4 key tiles x 2 query tiles
+__device__ __forceinline__ void fwd_scores(f32x4 (&s)[4][2], LDS_PTR(char) sk, const bf16x8 (&qf)[2][4], int lane) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) s[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const bf16x8 kf = frag_rm(sk, i * 16, kk, lane);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) s[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[j][kk], s[i][j], 0, 0, 0);
+        }
+    }
+}
+
+// O^T += V^T P^T : k = keys (two 32-key steps), 8 d tiles
+__device__ __forceinline__ void fwd_pv(f32x4 (&o)[8][2], const f32x4 (&s)[4][2], LDS_PTR(char) sv, int lane) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        bf16x8 pf[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) pf[j] = pack_frag(s[2 * a][j], s[2 * a + 1][j]);
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {
+            const bf16x8 vf = frag_tr(sv, a * 32, a * 32 + 16, dt * 16, lane);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) o[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[j], o[dt][j], 0, 0, 0);
+        }
+    }
+}
+
+// scores, mask + online softmax of m2 / l / o (per query = per lane&15), P V
+template <class KeyOk>
+__device__ __forceinline__ void fwd_tile(f32x4 (&o)[8][2], float (&m2)[2], float (&l)[2], LDS_PTR(char) sk, LDS_PTR(char) sv,
+                                         const bf16x8 (&qf)[2][4], int key0, bool interior, KeyOk key_ok, float scale2, int lane) {
+    const int g = lane >> 4;
+    f32x4 s[4][2];
+    fwd_scores(s, sk, qf, lane);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        float mx = -INFINITY;                          // max of the RAW scores (scale2 > 0 commutes with max)
+        if (interior) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][j][r]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = key_ok(key0 + i * 16 + g * 4 + r, j) ? s[i][j][r] : -INFINITY;
+                    s[i][j][r] = v;
+                    mx = fmaxf(mx, v);
+                }
+        }
+        mx = grp_max(mx) * scale2;
+        const float mn = fmaxf(m2[j], mx);
+        const float msafe = (mn == -INFINITY) ? 0.f : mn;
+        const float alpha = fast_exp2(m2[j] - msafe);   // m2=-inf -> 0
+        m2[j] = mn;
+        float rs_ = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float e = fast_exp2(fmaf(s[i][j][r], scale2, -msafe));   // masked: fma(-inf, +c, x) = -inf -> 0
+                s[i][j][r] = e;
+                rs_ += e;
+            }
+        l[j] = l[j] * alpha + rs_;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) o[dt][j] *= alpha;
+    }
+    fwd_pv(o, s, sv, lane);
+}
+
+// query tile j's output row, normalised, and its lse2 (+inf: a fully masked row) to op (the lane's 4 columns) / lse, if valid.
+// normalised: P was divided by the row sum before the PV product (HFR).  Every lane of the wave takes part in the row sum.
+__device__ __forceinline__ void fwd_store(const f32x4 (&o)[8][2], float m2, float l, int j, bool valid, bool normalised, bf16_t* op,
+                                          float* lse, int lane) {
+    const float lt = grp_sum(l);
+    const float inv = normalised ? (lt > 0.f ? 1.f : 0.f) : (lt > 0.f ? 1.f / lt : 0.f);
+    if (!valid) return;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+        u32x2 w = {pack2bf(o[dt][j][0] * inv, o[dt][j][1] * inv), pack2bf(o[dt][j][2] * inv, o[dt][j][3] * inv)};
+        *(u32x2*)(op + dt * 16) = w;
+    }
+    if ((lane >> 4) == 0) *lse = lt > 0.f ? m2 + log2f(lt) : INFINITY;
+}
+
+// grid (B*H, ceil(S/128)), 256 threads: wave w owns queries q0 + w*32 .. +31 (two 16-query tiles)
 //
 // HFR = false: the product kernel (flash style: fp32 scores, unnormalised bf16 P, one pass).
 // HFR = true : PARITY INSTRUMENT, not on the product path.  Reproduces the rounding points of HF's eager LlamaAttention
@@ -305,6 +403,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) o[dt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m2[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
+    auto key_ok = [&](int key, int j) { return key <= qpos[j] && key >= kvs; };
 
     const int q_hi = (q0 + 127 < S - 1) ? q0 + 127 : S - 1;   // last query of this block
     const int kt_beg = kvs / 64, kt_end = q_hi / 64;           // inclusive key-tile range
@@ -335,26 +434,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
             if (kt < kt_end) stage(kt + 1, cur ^ 1);
             LDS_PTR(char) sk = smem + cur * 2 * TILE;
             LDS_PTR(char) sv = sk + TILE;
-            // ---- S^T = K Q^T : 4 key tiles x 2 query tiles
-            f32x4 s[4][2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) s[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const bf16x8 kf = frag_rm(sk, i * 16, kk, lane);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        s[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[j][kk], s[i][j], 0, 0, 0);
-                }
-            }
-            // ---- mask + online softmax (per query = per lane&15).  Key tiles entirely below this wave's first query and
-            // entirely at/after the left padding need no mask at all (wave-uniform test): most tiles of a long prompt.
-            const bool interior = !HFR && (kt * 64 + 63 <= q0 + wave * 32) && (kt * 64 >= kvs);
-            if constexpr (HFR) {
+            if constexpr (!HFR) {
+                // key tiles entirely below this wave's first query and at/after the left padding
+                const bool interior = (kt * 64 + 63 <= q0 + wave * 32) && (kt * 64 >= kvs);
+                fwd_tile(o, m2, l, sk, sv, qf, kt * 64, interior, key_ok, p.scale2, lane);
+            } else {
+                f32x4 s[4][2];
+                fwd_scores(s, sk, qf, lane);
                 constexpr float LOG2E = 1.4426950408889634f;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -363,8 +449,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const int key = kt * 64 + i * 16 + g * 4 + r;
-                            const bool ok = (key <= qpos[j]) && (key >= kvs);
+                            const bool ok = key_ok(kt * 64 + i * 16 + g * 4 + r, j);
                             const float v = ok ? rbf(rbf(s[i][j][r]) * p.scale) * LOG2E : -INFINITY;   // HF's two bf16 roundings
                             s[i][j][r] = v;
                             mx = fmaxf(mx, v);
@@ -389,61 +474,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
                             for (int r = 0; r < 4; ++r) s[i][j][r] = fast_exp2(s[i][j][r] - msafe) * hf_inv[j];   // normalised P (bf16 in pack_frag)
                     }
                 }
-            } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                float mx = -INFINITY;                          // max of the RAW scores (scale2 > 0 commutes with max)
-                if (interior) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][j][r]);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = kt * 64 + i * 16 + g * 4 + r;
-                            const bool ok = (key <= qpos[j]) && (key >= kvs);
-                            const float v = ok ? s[i][j][r] : -INFINITY;
-                            s[i][j][r] = v;
-                            mx = fmaxf(mx, v);
-                        }
-                }
-                mx = grp_max(mx) * p.scale2;
-                const float mn = fmaxf(m2[j], mx);
-                const float msafe = (mn == -INFINITY) ? 0.f : mn;
-                const float alpha = fast_exp2(m2[j] - msafe);   // m2=-inf -> 0
-                m2[j] = mn;
-                float rs_ = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float e = fast_exp2(fmaf(s[i][j][r], p.scale2, -msafe));   // masked: fma(-inf, +c, x) = -inf -> 0
-                        s[i][j][r] = e;
-                        rs_ += e;
-                    }
-                l[j] = l[j] * alpha + rs_;
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) o[dt][j] *= alpha;
-            }
-            }
-            // ---- O^T += V^T P^T : k = keys (two 32-key steps), 8 d tiles
-            if (!HFR || pass == 1) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                bf16x8 pf[2];
-#pragma unroll
-                for (int j = 0; j < 2; ++j) pf[j] = pack_frag(s[2 * a][j], s[2 * a + 1][j]);
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) {
-                    const bf16x8 vf = frag_tr(sv, a * 32, a * 32 + 16, dt * 16, lane);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        o[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[j], o[dt][j], 0, 0, 0);
-                }
-            }
+                if (pass == 1) fwd_pv(o, s, sv, lane);
             }
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
@@ -451,27 +482,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         }
         }
     }
-    // ---- finalize
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float lt = grp_sum(l[j]);
-        const bool valid = qpos[j] < S;
-        const float inv = HFR ? (lt > 0.f ? 1.f : 0.f) : (lt > 0.f ? 1.f / lt : 0.f);   // HFR: P was normalised before the PV product
-        if (valid) {
-            bf16_t* op = p.out + (sq.row0 + qpos[j]) * (p.H * HD) + h * HD + g * 4;
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                u32x2 w = {pack2bf(o[dt][j][0] * inv, o[dt][j][1] * inv), pack2bf(o[dt][j][2] * inv, o[dt][j][3] * inv)};
-                *(u32x2*)(op + dt * 16) = w;
-            }
-            if (g == 0) p.lse2[((long)b * p.H + h) * lse_stride(p) + qpos[j]] = lt > 0.f ? m2[j] + log2f(lt) : INFINITY;
-        }
-    }
+    for (int j = 0; j < 2; ++j)
+        fwd_store(o, m2[j], l[j], j, qpos[j] < S, HFR, p.out + (sq.row0 + qpos[j]) * (p.H * HD) + h * HD + g * 4,
+                  p.lse2 + ((long)b * p.H + h) * lse_stride(p) + qpos[j], lane);
 }
 
 // =========================================================================== episode forward (round 5)
-// The forward twin of the episode backward kernels below: the steps of a prefix-reuse episode (navillm_amd/episode.py) keep their
-// q|k|v rows in per-layer episode buffers -- prefix rows of sample b at [cu[b], cu[b+1]), step t's rows of sample b at
+// Tile step: fwd_tile, as in attn_fwd_kernel; only the row addressing and the mask differ.  The steps of a prefix-reuse episode
+// (navillm_amd/episode.py) keep their q|k|v rows in per-layer episode buffers -- prefix rows of sample b at [cu[b], cu[b+1]), step t's rows of sample b at
 // [off[t,b], off[t,b] + n[t,b]) -- and a step's queries see their sample's whole prefix and the step's own earlier rows.  Round 4 ran
 // the batched (teacher-forced) forward's attention per step through the K/V-cache layout: scatter the step's rows into the cache,
 // one strided forward launch, gather the outputs back -- 18 launches per layer for six steps.  This kernel reads the row buffers in
@@ -556,90 +575,17 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
         if (kt < kt_end) stage(kt + 1, cur ^ 1);
         LDS_PTR(char) sk = smem + cur * 2 * TILE;
         LDS_PTR(char) sv = sk + TILE;
-        f32x4 s[4][2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) s[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bf16x8 kf = frag_rm(sk, i * 16, kk, lane);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) s[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[j][kk], s[i][j], 0, 0, 0);
-            }
-        }
-        const bool interior = kt * 64 + 63 <= lp + q0 + wave * 32;      // (same test as attn_fwd_kernel, in virtual positions)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float mx = -INFINITY;
-            if (interior) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[i][j][r]);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = kt * 64 + i * 16 + g * 4 + r;
-                        const float v = key <= qpos[j] ? s[i][j][r] : -INFINITY;
-                        s[i][j][r] = v;
-                        mx = fmaxf(mx, v);
-                    }
-            }
-            mx = grp_max(mx) * p.scale2;
-            const float mn = fmaxf(m2[j], mx);
-            const float msafe = (mn == -INFINITY) ? 0.f : mn;
-            const float alpha = fast_exp2(m2[j] - msafe);
-            m2[j] = mn;
-            float rs_ = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float e = fast_exp2(fmaf(s[i][j][r], p.scale2, -msafe));
-                    s[i][j][r] = e;
-                    rs_ += e;
-                }
-            l[j] = l[j] * alpha + rs_;
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) o[dt][j] *= alpha;
-        }
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            bf16x8 pf[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) pf[j] = pack_frag(s[2 * a][j], s[2 * a + 1][j]);
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                const bf16x8 vf = frag_tr(sv, a * 32, a * 32 + 16, dt * 16, lane);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) o[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[j], o[dt][j], 0, 0, 0);
-            }
-        }
+        const bool interior = kt * 64 + 63 <= lp + q0 + wave * 32;      // the tile lies before this wave's first (virtual) query
+        fwd_tile(o, m2, l, sk, sv, qf, kt * 64, interior, [&](int key, int j) { return key <= qpos[j]; }, p.scale2, lane);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         cur ^= 1;
     }
     float* lse2 = p.lse[t] + ((long)b * p.H + h) * p.cap;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const float lt = grp_sum(l[j]);
-        const int jl = qpos[j] - lp;
-        if (jl < n) {
-            const float inv = lt > 0.f ? 1.f / lt : 0.f;
-            bf16_t* op = p.out + ((long)off + jl) * (p.H * HD) + h * HD + g * 4;
-#pragma unroll
-            for (int dt = 0; dt < 8; ++dt) {
-                u32x2 w = {pack2bf(o[dt][j][0] * inv, o[dt][j][1] * inv), pack2bf(o[dt][j][2] * inv, o[dt][j][3] * inv)};
-                *(u32x2*)(op + dt * 16) = w;
-            }
-            if (g == 0) lse2[qpos[j]] = lt > 0.f ? m2[j] + log2f(lt) : INFINITY;
-        }
-    }
+    for (int j = 0; j < 2; ++j)
+        fwd_store(o, m2[j], l[j], j, qpos[j] - lp < n, false, p.out + ((long)off + qpos[j] - lp) * (p.H * HD) + h * HD + g * 4,
+                  lse2 + qpos[j], lane);
 }
 
 // =========================================================================== backward prep
@@ -676,9 +622,97 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const bf16_t* __rest
 }
 
 // =========================================================================== backward dK, dV
-// grid (ceil(S/(64*KW)), B*H), 256 threads: wave w owns KW key tiles of 16 (keys kblk + (w*KW+jk)*16 ..); walks query
-// tiles of 32.  KW = 2 halves the LDS fragment traffic per MFMA (every Q/dO fragment feeds two key tiles).
-template <int KW>
+// The tile step of both dK/dV kernels (attn_bwd_dkv_kernel, epi_bwd_dkv_kernel): one 32-query tile (Q at tq, dO at tdo) against a
+// wave's 16 keys (fragments kf, vf).  A lane holds key lane&15 and the queries q0 + j*16 + g*4 + r, whose lse2 and dsum are lq / dsq;
+// q_ok(q) = may this lane's key be seen by query q (not evaluated when interior: no pair of the tile is masked).
+//   S = Q K^T, dP = dO V^T ; P = exp2(S scale2 - lse2), dS = P (dP - dsum) ; dV^T += dO^T P, dK^T += Q^T dS
+template <class QOk>
+__device__ __forceinline__ void dkv_tile(f32x4 (&dk)[8], f32x4 (&dv)[8], LDS_PTR(char) tq, LDS_PTR(char) tdo, const bf16x8 (&kf)[4],
+                                         const bf16x8 (&vf)[4], const float (&lq)[2][4], const float (&dsq)[2][4], int q0, bool interior,
+                                         QOk q_ok, float scale2, int lane) {
+    const int g = lane >> 4;
+    f32x4 s[2], dp[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    // the row-major fragments of two k-steps are requested back to back, then their eight MFMAs run while the later reads are
+    // still in flight (second phase: four head-dim tiles at a time).  With two waves per SIMD nothing else hides the LDS
+    // latency; hipcc's own schedule keeps ONE read ahead of its MFMA, and sched_barrier stops it from re-interleaving this one.
+    // (All sixteen at once, plus the second phase's first half before the softmax arithmetic: 220 VGPRs and no faster.)
+#pragma unroll
+    for (int k2 = 0; k2 < 2; ++k2) {
+        bf16x8 qa[2][2], da[2][2];
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                qa[kk][j] = frag_rm(tq, j * 16, k2 * 2 + kk, lane);
+                da[kk][j] = frag_rm(tdo, j * 16, k2 * 2 + kk, lane);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kk][j], kf[k2 * 2 + kk], s[j], 0, 0, 0);
+                dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[kk][j], vf[k2 * 2 + kk], dp[j], 0, 0, 0);
+            }
+    }
+    f32x4 pv[2], ds[2];
+    if (interior) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pe = fast_exp2(fmaf(s[j][r], scale2, -lq[j][r]));
+                pv[j][r] = pe;
+                ds[j][r] = pe * (dp[j][r] - dsq[j][r]);
+            }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool ok = q_ok(q0 + j * 16 + g * 4 + r);
+                const float pe = ok ? fast_exp2(fmaf(s[j][r], scale2, -lq[j][r])) : 0.f;
+                pv[j][r] = pe;
+                ds[j][r] = pe * (dp[j][r] - dsq[j][r]);
+            }
+    }
+    const bf16x8 pfrag = pack_frag(pv[0], pv[1]), dsfrag = pack_frag(ds[0], ds[1]);
+    // k = the 32 queries, permuted as pack_frag lays them
+#pragma unroll
+    for (int d4 = 0; d4 < 2; ++d4) {
+        bf16x8 dot_[4], qt_[4];
+#pragma unroll
+        for (int dd = 0; dd < 4; ++dd) {
+            dot_[dd] = frag_tr(tdo, 0, 16, (d4 * 4 + dd) * 16, lane);
+            qt_[dd] = frag_tr(tq, 0, 16, (d4 * 4 + dd) * 16, lane);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int dd = 0; dd < 4; ++dd) {
+            dv[d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot_[dd], pfrag, dv[d4 * 4 + dd], 0, 0, 0);
+            dk[d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt_[dd], dsfrag, dk[d4 * 4 + dd], 0, 0, 0);
+        }
+    }
+}
+
+// A cached prefix key row: its dK | dV are summed over an episode's steps in fp32 and no bf16 row is written (what
+// nv_kv_grad_accum_f32 did from the bf16 row in a second pass: 342 MB per layer and step at 7B/B=8).  ak = the lane's dK columns of
+// the row in the fp32 accumulator [rows, 2*H*HD], its dV columns od = H*HD floats later; same scaling as the bf16 store, no
+// rounding.  add: onto the accumulator's value, else over it.
+__device__ __forceinline__ void store_kvacc_row(float* ak, int od, const f32x4 (&dk)[8], const f32x4 (&dv)[8], float scale, int add) {
+    float* av = ak + od;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) {
+        f32x4 k4 = dk[dt] * scale, v4 = dv[dt];
+        if (add) { k4 += *(const f32x4*)(ak + dt * 16); v4 += *(const f32x4*)(av + dt * 16); }
+        *(f32x4*)(ak + dt * 16) = k4;
+        *(f32x4*)(av + dt * 16) = v4;
+    }
+}
+
+// grid (B*H, ceil(S/64)), 256 threads: wave w owns the 16 keys kblk + w*16 ..; walks query tiles of 32.
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
@@ -687,7 +721,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;      // grid (B*H, key blocks): key block 0 (all queries) goes first
     const Seq sq = seq_of(p, b);
     const int S = sq.S, ld = p.ld;
-    const int kblk = blockIdx.y * 64 * KW;
+    const int kblk = blockIdx.y * 64;
     if (kblk >= S) return;
     const int kvs = sq.kvs;
     const int ki = lane & 15, g = lane >> 4;
@@ -701,25 +735,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     const float* dsum = p.dsum + ((long)b * p.H + h) * lse_stride(p);
 
     // K and V fragments (B operand: j = key, k = head dim) from HBM
-    bf16x8 kf[KW][4], vf[KW][4];
-    int key[KW];
-#pragma unroll
-    for (int jk = 0; jk < KW; ++jk) {
-        key[jk] = kblk + (wave * KW + jk) * 16 + ki;
-        const int kl = key[jk] < S ? key[jk] : S - 1;
+    const int key = kblk + wave * 16 + ki;
+    bf16x8 kf[4], vf[4];
+    {
+        const int kl = key < S ? key : S - 1;
         const bf16_t* kp = base + (long)kl * ld + p.H * HD + h * HD + g * 8;
         const bf16_t* vp = base + (long)kl * ld + 2 * p.H * HD + h * HD + g * 8;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            kf[jk][kk] = *(const bf16x8*)(kp + kk * 32);
-            vf[jk][kk] = *(const bf16x8*)(vp + kk * 32);
+            kf[kk] = *(const bf16x8*)(kp + kk * 32);
+            vf[kk] = *(const bf16x8*)(vp + kk * 32);
         }
     }
-    f32x4 dv[KW][8], dk[KW][8];
+    f32x4 dv[8], dk[8];
 #pragma unroll
-    for (int jk = 0; jk < KW; ++jk)
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) { dv[jk][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[jk][dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int dt = 0; dt < 8; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
     // queries that can see this key block: q >= kblk (causal), q >= kvs (pad queries have p=0 anyway)
     const int qt_lo = sq.qmin / 32;
@@ -749,20 +779,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     if (qt_beg < qt_end) stage(qt_beg + 1, 1);
     if (qt_beg + 1 < qt_end) stage(qt_beg + 2, 2);
 #pragma unroll
-    for (int jk = 0; jk < KW; ++jk)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) { pin(kf[jk][kk]); pin(vf[jk][kk]); }
+    for (int kk = 0; kk < 4; ++kk) { pin(kf[kk]); pin(vf[kk]); }
     wait_stages(qt_end - qt_beg);
     __builtin_amdgcn_s_barrier();
     int cur = 0;
+    const int wkey_lo = kblk + wave * 16, wkey_hi = wkey_lo + 15;
     for (int qt = qt_beg; qt <= qt_end; ++qt) {
-        float lq[2][4], dq_[2][4];
+        float lq[2][4], dsq[2][4];
         if (p.stat_cap) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const f32x4 a4 = *(LDS_PTR(f32x4))(s_lse + qt * 32 + j * 16 + g * 4), d4 = *(LDS_PTR(f32x4))(s_ds + qt * 32 + j * 16 + g * 4);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { lq[j][r] = a4[r]; dq_[j][r] = d4[r]; }
+                for (int r = 0; r < 4; ++r) { lq[j][r] = a4[r]; dsq[j][r] = d4[r]; }
             }
         } else {
 #pragma unroll
@@ -772,123 +801,90 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
                     const int q = qt * 32 + j * 16 + g * 4 + r;
                     const int qc = q < S ? q : S - 1;
                     lq[j][r] = lse2[qc];
-                    dq_[j][r] = dsum[qc];
+                    dsq[j][r] = dsum[qc];
                 }
         }
         if (qt + 3 <= qt_end) stage(qt + 3, (cur + 3) & 3);
-        LDS_PTR(char) sq = smem + cur * 2 * TILE;
-        LDS_PTR(char) sdo = sq + TILE;
-        // ---- S = Q K^T and dP = dO V^T : lane holds key = lane&15, queries qt*32 + j*16 + g*4 + r
-        f32x4 s[KW][2], dp[KW][2];
-#pragma unroll
-        for (int jk = 0; jk < KW; ++jk)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { s[jk][j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[jk][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        // reads of two k-steps back to back, then their MFMAs (see epi_bwd_dkv_kernel)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-            bf16x8 qa[2][2], da[2][2];
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    qa[kk][j] = frag_rm(sq, j * 16, k2 * 2 + kk, lane);
-                    da[kk][j] = frag_rm(sdo, j * 16, k2 * 2 + kk, lane);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int jk = 0; jk < KW; ++jk) {
-                        s[jk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kk][j], kf[jk][k2 * 2 + kk], s[jk][j], 0, 0, 0);
-                        dp[jk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[kk][j], vf[jk][k2 * 2 + kk], dp[jk][j], 0, 0, 0);
-                    }
-        }
-        bf16x8 pfrag[KW], dsfrag[KW];
-        // query tiles entirely past this wave's keys, inside [0, S), with the keys past the left padding: no mask
-        const int wkey_lo = kblk + wave * KW * 16, wkey_hi = wkey_lo + KW * 16 - 1;
+        LDS_PTR(char) tq = smem + cur * 2 * TILE;
+        // query tiles entirely past this wave's keys, inside [0, S), with the keys past the left padding
         const bool interior = (qt * 32 >= wkey_hi) && (qt * 32 + 31 < S) && (wkey_lo >= kvs) && (wkey_hi < S);
-#pragma unroll
-        for (int jk = 0; jk < KW; ++jk) {
-            f32x4 pv[2], ds[2];
-            if (interior) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float pe = fast_exp2(fmaf(s[jk][j][r], p.scale2, -lq[j][r]));
-                        pv[j][r] = pe;
-                        ds[j][r] = pe * (dp[jk][j][r] - dq_[j][r]);
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int q = qt * 32 + j * 16 + g * 4 + r;
-                        const bool ok = (q < S) && (key[jk] <= q) && (key[jk] >= kvs) && (key[jk] < S);
-                        const float pe = ok ? fast_exp2(fmaf(s[jk][j][r], p.scale2, -lq[j][r])) : 0.f;
-                        pv[j][r] = pe;
-                        ds[j][r] = pe * (dp[jk][j][r] - dq_[j][r]);
-                    }
-            }
-            pfrag[jk] = pack_frag(pv[0], pv[1]);
-            dsfrag[jk] = pack_frag(ds[0], ds[1]);
-        }
-        // ---- dV^T += dO^T P ; dK^T += Q^T dS   (k = the 32 queries, permuted as pack_frag lays them)
-#pragma unroll
-        for (int d4 = 0; d4 < 2; ++d4) {
-            bf16x8 dot_[4], qt_[4];
-#pragma unroll
-            for (int dd = 0; dd < 4; ++dd) {
-                dot_[dd] = frag_tr(sdo, 0, 16, (d4 * 4 + dd) * 16, lane);
-                qt_[dd] = frag_tr(sq, 0, 16, (d4 * 4 + dd) * 16, lane);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int dd = 0; dd < 4; ++dd)
-#pragma unroll
-                for (int jk = 0; jk < KW; ++jk) {
-                    dv[jk][d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot_[dd], pfrag[jk], dv[jk][d4 * 4 + dd], 0, 0, 0);
-                    dk[jk][d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt_[dd], dsfrag[jk], dk[jk][d4 * 4 + dd], 0, 0, 0);
-                }
-        }
+        dkv_tile(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, qt * 32, interior,
+                 [&](int q) { return q < S && key <= q && key >= kvs && key < S; }, p.scale2, lane);
         wait_stages(qt_end - (qt + 1));                                     // tile qt+1 has landed (qt+2, qt+3 may be in flight)
         __builtin_amdgcn_s_barrier();
         cur = (cur + 1) & 3;
     }
     }
-    const int acc_len = p.kvacc ? p.kvacc_len[b] : 0;
-#pragma unroll
-    for (int jk = 0; jk < KW; ++jk)
-        if (key[jk] < S) {
-            if (key[jk] < acc_len) {
-                // a cached prefix row: its K/V gradient is summed over the episode's steps in fp32 (what nv_kv_grad_accum_f32 did from
-                // the bf16 row in a second pass: 342 MB per layer and step at 7B/B=8); same scaling as the bf16 store, no rounding
-                float* ak = p.kvacc + (sq.row0 + key[jk]) * (2L * p.H * HD) + h * HD + g * 4;
-                float* av = ak + p.H * HD;
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) {
-                    f32x4 k4 = dk[jk][dt] * p.scale, v4 = dv[jk][dt];
-                    if (!p.kvacc_first) { k4 += *(const f32x4*)(ak + dt * 16); v4 += *(const f32x4*)(av + dt * 16); }
-                    *(f32x4*)(ak + dt * 16) = k4;
-                    *(f32x4*)(av + dt * 16) = v4;
-                }
-                continue;
-            }
-            bf16_t* kp = p.dqkv + (sq.row0 + key[jk]) * ld + p.H * HD + h * HD + g * 4;
-            bf16_t* vp = p.dqkv + (sq.row0 + key[jk]) * ld + 2 * p.H * HD + h * HD + g * 4;
-            store_grad_row(kp, dk[jk], p.scale, p.rope_cos ? p.rope_cos + (long)(key[jk] + sq.pos0) * HD + g * 4 : nullptr,
-                           p.rope_sin ? p.rope_sin + (long)(key[jk] + sq.pos0) * HD + g * 4 : nullptr);
-            store_grad_row(vp, dv[jk], 1.f, nullptr, nullptr);
-        }
+    if (key >= S) return;
+    if (p.kvacc && key < p.kvacc_len[b]) {
+        store_kvacc_row(p.kvacc + (sq.row0 + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
+        return;
+    }
+    bf16_t* kp = p.dqkv + (sq.row0 + key) * ld + p.H * HD + h * HD + g * 4;
+    store_grad_row(kp, dk, p.scale, p.rope_cos ? p.rope_cos + (long)(key + sq.pos0) * HD + g * 4 : nullptr,
+                   p.rope_sin ? p.rope_sin + (long)(key + sq.pos0) * HD + g * 4 : nullptr);
+    store_grad_row(kp + p.H * HD, dv, 1.f, nullptr, nullptr);
 }
 
 // =========================================================================== backward dQ
-// grid (ceil((S-q_row_min)/(64*QW)), B*H), 256 threads: wave w owns QW query tiles of 16; walks key tiles of 64.
-template <int QW>
+// The tile step of both dQ kernels (attn_bwd_dq_kernel, epi_bwd_dq_kernel): one 64-key tile (K at sk, V at sv) against a wave's 16
+// queries (fragments qf, dof; lse2 and dsum of the lane's query).  A lane holds query lane&15 and the keys key0 + i*16 + g*4 + r;
+// key_ok(key) = may the lane's query see that key (not evaluated when interior: no pair of the tile is masked).
+//   S^T = K Q^T, dP^T = V dO^T ; dS^T = P (dP - dsum) ; dQ^T += K^T dS^T
+template <class KeyOk>
+__device__ __forceinline__ void dq_tile(f32x4 (&dq)[8], LDS_PTR(char) sk, LDS_PTR(char) sv, const bf16x8 (&qf)[4], const bf16x8 (&dof)[4],
+                                        float lse, float dsq, int key0, bool interior, KeyOk key_ok, float scale2, int lane) {
+    const int g = lane >> 4;
+    f32x4 s[4], dp[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { s[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    // one k-step's eight fragment reads back to back, then its MFMAs (see dkv_tile)
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        bf16x8 ka[4], va[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ka[i] = frag_rm(sk, i * 16, kk, lane);
+            va[i] = frag_rm(sv, i * 16, kk, lane);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            s[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[i], qf[kk], s[i], 0, 0, 0);
+            dp[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[i], dof[kk], dp[i], 0, 0, 0);
+        }
+    }
+    if (interior) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float pe = fast_exp2(fmaf(s[i][r], scale2, -lse));
+                s[i][r] = pe * (dp[i][r] - dsq);   // dS^T
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const bool ok = key_ok(key0 + i * 16 + g * 4 + r);
+                const float pe = ok ? fast_exp2(fmaf(s[i][r], scale2, -lse)) : 0.f;
+                s[i][r] = pe * (dp[i][r] - dsq);
+            }
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const bf16x8 dsf = pack_frag(s[2 * a], s[2 * a + 1]);
+        bf16x8 kt_[8];
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) kt_[dt] = frag_tr(sk, a * 32, a * 32 + 16, dt * 16, lane);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf, dq[dt], 0, 0, 0);
+    }
+}
+
+// grid (B*H, ceil((S-q_row_min)/64)), 256 threads: wave w owns 16 queries; walks key tiles of 64.
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
@@ -897,7 +893,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;      // grid (B*H, query blocks), last (longest) query block first
     const Seq sq = seq_of(p, b);
     const int S = sq.S, ld = p.ld;
-    const int q0 = sq.qmin + (gridDim.y - 1 - blockIdx.y) * 64 * QW;
+    const int q0 = sq.qmin + (gridDim.y - 1 - blockIdx.y) * 64;
     if (q0 >= S) return;
     const int kvs = sq.kvs;
     const int qi = lane & 15, g = lane >> 4;
@@ -907,30 +903,26 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     const int od = p.H * HD;
     const int kcol = p.H * HD + h * HD, vcol = 2 * p.H * HD + h * HD;
 
-    bf16x8 qf[QW][4], dof[QW][4];
-    int q[QW];
-    float my_lse[QW], my_ds[QW];
-#pragma unroll
-    for (int j = 0; j < QW; ++j) {
-        q[j] = q0 + (wave * QW + j) * 16 + qi;
-        const int ql = q[j] < S ? q[j] : S - 1;
+    const int q = q0 + wave * 16 + qi;
+    bf16x8 qf[4], dof[4];
+    float my_lse, my_ds;
+    {
+        const int ql = q < S ? q : S - 1;
         const bf16_t* qp = base + (long)ql * ld + h * HD + g * 8;
         const bf16_t* dp_ = p.dout + (sq.row0 + ql) * od + h * HD + g * 8;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            qf[j][kk] = *(const bf16x8*)(qp + kk * 32);
-            dof[j][kk] = *(const bf16x8*)(dp_ + kk * 32);
+            qf[kk] = *(const bf16x8*)(qp + kk * 32);
+            dof[kk] = *(const bf16x8*)(dp_ + kk * 32);
         }
-        my_lse[j] = p.lse2[((long)b * p.H + h) * lse_stride(p) + ql];
-        my_ds[j] = p.dsum[((long)b * p.H + h) * lse_stride(p) + ql];
+        my_lse = p.lse2[((long)b * p.H + h) * lse_stride(p) + ql];
+        my_ds = p.dsum[((long)b * p.H + h) * lse_stride(p) + ql];
     }
-    f32x4 dq[QW][8];
+    f32x4 dq[8];
 #pragma unroll
-    for (int j = 0; j < QW; ++j)
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) dq[j][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < 8; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int q_hi = (q0 + 64 * QW - 1 < S - 1) ? q0 + 64 * QW - 1 : S - 1;
+    const int q_hi = (q0 + 63 < S - 1) ? q0 + 63 : S - 1;
     const int kt_beg = kvs / 64, kt_end = q_hi / 64;
     if (kt_beg <= kt_end) {
         auto stage = [&](int kt, int buf) {
@@ -939,92 +931,28 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
         };
         stage(kt_beg, 0);
 #pragma unroll
-        for (int j = 0; j < QW; ++j) {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) { pin(qf[j][kk]); pin(dof[j][kk]); }
-            pin(my_lse[j]); pin(my_ds[j]);
-        }
+        for (int kk = 0; kk < 4; ++kk) { pin(qf[kk]); pin(dof[kk]); }
+        pin(my_lse); pin(my_ds);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         int cur = 0;
+        const int wq_lo = q0 + wave * 16;
         for (int kt = kt_beg; kt <= kt_end; ++kt) {
             if (kt < kt_end) stage(kt + 1, cur ^ 1);
             LDS_PTR(char) sk = smem + cur * 2 * TILE;
-            LDS_PTR(char) sv = sk + TILE;
-            f32x4 s[4][QW], dp[4][QW];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < QW; ++j) { s[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            // one k-step's eight fragment reads back to back, then its MFMAs (see epi_bwd_dkv_kernel)
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                bf16x8 ka[4], va[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    ka[i] = frag_rm(sk, i * 16, kk, lane);
-                    va[i] = frag_rm(sv, i * 16, kk, lane);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < QW; ++j) {
-                        s[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[i], qf[j][kk], s[i][j], 0, 0, 0);
-                        dp[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[i], dof[j][kk], dp[i][j], 0, 0, 0);
-                    }
-            }
-            // key tiles entirely before this wave's first query, past the left padding, with all its queries < S: no mask
-            const int wq_lo = q0 + wave * QW * 16;
-            const bool interior = (kt * 64 + 63 <= wq_lo) && (kt * 64 >= kvs) && (wq_lo + QW * 16 - 1 < S);
-#pragma unroll
-            for (int j = 0; j < QW; ++j) {
-                if (interior) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float pe = fast_exp2(fmaf(s[i][j][r], p.scale2, -my_lse[j]));
-                            s[i][j][r] = pe * (dp[i][j][r] - my_ds[j]);   // dS^T
-                        }
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int key = kt * 64 + i * 16 + g * 4 + r;
-                            const bool ok = (q[j] < S) && (key <= q[j]) && (key >= kvs);
-                            const float pe = ok ? fast_exp2(fmaf(s[i][j][r], p.scale2, -my_lse[j])) : 0.f;
-                            s[i][j][r] = pe * (dp[i][j][r] - my_ds[j]);   // dS^T
-                        }
-                }
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                bf16x8 dsf[QW];
-#pragma unroll
-                for (int j = 0; j < QW; ++j) dsf[j] = pack_frag(s[2 * a][j], s[2 * a + 1][j]);
-                bf16x8 kt_[8];
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) kt_[dt] = frag_tr(sk, a * 32, a * 32 + 16, dt * 16, lane);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-                    for (int j = 0; j < QW; ++j) dq[j][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf[j], dq[j][dt], 0, 0, 0);
-            }
+            // key tiles entirely before this wave's first query, past the left padding, with all its queries < S
+            const bool interior = (kt * 64 + 63 <= wq_lo) && (kt * 64 >= kvs) && (wq_lo + 15 < S);
+            dq_tile(dq, sk, sk + TILE, qf, dof, my_lse, my_ds, kt * 64, interior,
+                    [&](int key) { return q < S && key <= q && key >= kvs; }, p.scale2, lane);
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             cur ^= 1;
         }
     }
-#pragma unroll
-    for (int j = 0; j < QW; ++j)
-        if (q[j] < S) {
-            bf16_t* qp = p.dqkv + (sq.row0 + q[j]) * ld + h * HD + g * 4;
-            store_grad_row(qp, dq[j], p.scale, p.rope_cos ? p.rope_cos + (long)(q[j] + sq.pos0) * HD + g * 4 : nullptr,
-                           p.rope_sin ? p.rope_sin + (long)(q[j] + sq.pos0) * HD + g * 4 : nullptr);
-        }
+    if (q >= S) return;
+    bf16_t* qp = p.dqkv + (sq.row0 + q) * ld + h * HD + g * 4;
+    store_grad_row(qp, dq, p.scale, p.rope_cos ? p.rope_cos + (long)(q + sq.pos0) * HD + g * 4 : nullptr,
+                   p.rope_sin ? p.rope_sin + (long)(q + sq.pos0) * HD + g * 4 : nullptr);
 }
 
 // =========================================================================== backward of a prefix-reuse EPISODE's steps (round 3)
@@ -1149,81 +1077,18 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
                 __syncthreads();
                 t_stats = t0;
             }
-            float lq[2][4], dq_[2][4];
+            float lq[2][4], dsq[2][4];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const f32x4 a4 = *(LDS_PTR(f32x4))(s_lse + q0 * 32 + j * 16 + g * 4), d4 = *(LDS_PTR(f32x4))(s_ds + q0 * 32 + j * 16 + g * 4);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { lq[j][r] = a4[r]; dq_[j][r] = d4[r]; }
+                for (int r = 0; r < 4; ++r) { lq[j][r] = a4[r]; dsq[j][r] = d4[r]; }
             }
             if (more) stage(t3, q3, (cur + 3) & 3);
-            LDS_PTR(char) sq = smem + cur * 2 * TILE;
-            LDS_PTR(char) sdo = sq + TILE;
-            f32x4 s[2], dp[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) { s[j] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[j] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            // the row-major fragments of two k-steps are requested back to back, then their eight MFMAs run while the later reads are
-            // still in flight (second phase: four head-dim tiles at a time).  With two waves per SIMD nothing else hides the LDS
-            // latency; hipcc's own schedule keeps ONE read ahead of its MFMA, and sched_barrier stops it from re-interleaving this one.
-            // (All sixteen at once, plus the second phase's first half before the softmax arithmetic: 220 VGPRs and no faster.)
-#pragma unroll
-            for (int k2 = 0; k2 < 2; ++k2) {
-                bf16x8 qa[2][2], da[2][2];
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        qa[kk][j] = frag_rm(sq, j * 16, k2 * 2 + kk, lane);
-                        da[kk][j] = frag_rm(sdo, j * 16, k2 * 2 + kk, lane);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[kk][j], kf[k2 * 2 + kk], s[j], 0, 0, 0);
-                        dp[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da[kk][j], vf[k2 * 2 + kk], dp[j], 0, 0, 0);
-                    }
-            }
+            LDS_PTR(char) tq = smem + cur * 2 * TILE;
             const bool interior = (q0 * 32 + 31 < n) && (pre ? wkey_hi < lp : q0 * 32 >= wkey_hi);
-            f32x4 pv[2], ds[2];
-            if (interior) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float pe = fast_exp2(fmaf(s[j][r], p.scale2, -lq[j][r]));
-                        pv[j][r] = pe;
-                        ds[j][r] = pe * (dp[j][r] - dq_[j][r]);
-                    }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int q = q0 * 32 + j * 16 + g * 4 + r;
-                        const bool ok = (q < n) && (pre ? key < lp : key <= q);
-                        const float pe = ok ? fast_exp2(fmaf(s[j][r], p.scale2, -lq[j][r])) : 0.f;
-                        pv[j][r] = pe;
-                        ds[j][r] = ok ? pe * (dp[j][r] - dq_[j][r]) : 0.f;
-                    }
-            }
-            const bf16x8 pfrag = pack_frag(pv[0], pv[1]), dsfrag = pack_frag(ds[0], ds[1]);
-#pragma unroll
-            for (int d4 = 0; d4 < 2; ++d4) {
-                bf16x8 dot_[4], qt_[4];
-#pragma unroll
-                for (int dd = 0; dd < 4; ++dd) {
-                    dot_[dd] = frag_tr(sdo, 0, 16, (d4 * 4 + dd) * 16, lane);
-                    qt_[dd] = frag_tr(sq, 0, 16, (d4 * 4 + dd) * 16, lane);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int dd = 0; dd < 4; ++dd) {
-                    dv[d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot_[dd], pfrag, dv[d4 * 4 + dd], 0, 0, 0);
-                    dk[d4 * 4 + dd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt_[dd], dsfrag, dk[d4 * 4 + dd], 0, 0, 0);
-                }
-            }
+            dkv_tile(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, q0 * 32, interior, [&](int q) { return q < n && (pre ? key < lp : key <= q); },
+                     p.scale2, lane);
             wait_stages((t2 < t_end) + (more ? 1 : 0));                       // tile 1 has landed (tiles 2, 3 may be in flight)
             __builtin_amdgcn_s_barrier();
             cur = (cur + 1) & 3;
@@ -1233,15 +1098,7 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
     }
     if (key >= klen) return;
     if (pre) {
-        float* ak = p.kvacc + ((long)b * p.cap + key) * (2L * p.H * HD) + h * HD + g * 4;
-        float* av = ak + p.H * HD;
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
-            f32x4 k4 = dk[dt] * p.scale, v4 = dv[dt];
-            if (p.kvacc_add) { k4 += *(const f32x4*)(ak + dt * 16); v4 += *(const f32x4*)(av + dt * 16); }
-            *(f32x4*)(ak + dt * 16) = k4;
-            *(f32x4*)(av + dt * 16) = v4;
-        }
+        store_kvacc_row(p.kvacc + ((long)b * p.cap + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
         return;
     }
     const int pos = lp + key < p.cap ? lp + key : p.cap - 1;
@@ -1309,57 +1166,11 @@ __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
         for (int i = 0; i < total; ++i) {
             if (i + 1 < total) stage(i + 1, cur ^ 1);
             LDS_PTR(char) sk = smem + cur * 2 * TILE;
-            LDS_PTR(char) sv = sk + TILE;
             const bool is_pre = i < npt;
             const int kt = is_pre ? i : i - npt;
-            f32x4 s[4], dp[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) { s[a] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[a] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                bf16x8 ka[4], va[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    ka[a] = frag_rm(sk, a * 16, kk, lane);
-                    va[a] = frag_rm(sv, a * 16, kk, lane);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    s[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka[a], qf[kk], s[a], 0, 0, 0);
-                    dp[a] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(va[a], dof[kk], dp[a], 0, 0, 0);
-                }
-            }
             const bool interior = (wq_hi < n) && (is_pre ? kt * 64 + 63 < lp : kt * 64 + 63 <= wq_lo);
-            if (interior) {
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float pe = fast_exp2(fmaf(s[a][r], p.scale2, -lse_q));
-                        s[a][r] = pe * (dp[a][r] - ds_q);
-                    }
-            } else {
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int key = kt * 64 + a * 16 + g * 4 + r;
-                        const bool ok = (q < n) && (is_pre ? key < lp : key <= q);
-                        const float pe = ok ? fast_exp2(fmaf(s[a][r], p.scale2, -lse_q)) : 0.f;
-                        s[a][r] = ok ? pe * (dp[a][r] - ds_q) : 0.f;
-                    }
-            }
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const bf16x8 dsf = pack_frag(s[2 * a], s[2 * a + 1]);
-                bf16x8 kt_[8];
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) kt_[dt] = frag_tr(sk, a * 32, a * 32 + 16, dt * 16, lane);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int dt = 0; dt < 8; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf, dq[dt], 0, 0, 0);
-            }
+            dq_tile(dq, sk, sk + TILE, qf, dof, lse_q, ds_q, kt * 64, interior, [&](int key) { return q < n && (is_pre ? key < lp : key <= q); },
+                    p.scale2, lane);
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             cur ^= 1;
@@ -1510,21 +1321,14 @@ size_t nv_attn_bwd_workspace_bytes(int B, int S, int H) { return (size_t)B * S *
 static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const float* lse2, const int* kv_start, void* dqkv,
                          void* workspace, int B, int S, int H, int head_dim, int q_row_min, const void* rope_cos,
                          const void* rope_sin, void* stream, const int* cu = nullptr, long rows = -1, int Sst = 0, float* kvacc = nullptr,
-                         const int* kvacc_len = nullptr, int kvacc_first = 0) {
+                         const int* kvacc_len = nullptr, int kvacc_add = 0) {
     if (!qkv || !out || !dout || !lse2 || !kv_start || !dqkv || !workspace) return NV_ERR_ARG;
     if (head_dim != HD || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < (cu ? -1 : 0) || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
     if ((rope_cos == nullptr) != (rope_sin == nullptr)) return NV_ERR_ARG;
     if (B == 0 || S == 0) return NV_OK;
-    // measurement/test knob: 1 (default) = 16 rows per wave, 2 = 32 rows per wave.  Measured at B=8, S=656, H=32: the
-    // 32-row form halves the LDS fragment reads per MFMA but runs 539 vs 344 us -- with one barrier-synchronised tile
-    // step per iteration these kernels live on occupancy, which the wider form halves.
-    const char* ev = getenv("NV_ATTN_BWD_VARIANT");
-    const int variant = ev ? atoi(ev) : 1;
     static bool once = false;
     if (!once) {
-        if (set_lds((const void*)attn_bwd_dkv_kernel<1>, 77824) || set_lds((const void*)attn_bwd_dq_kernel<1>, 65536) ||
-            set_lds((const void*)attn_bwd_dkv_kernel<2>, 77824) || set_lds((const void*)attn_bwd_dq_kernel<2>, 65536))
-            return NV_ERR_LAUNCH;
+        if (set_lds((const void*)attn_bwd_dkv_kernel, 77824) || set_lds((const void*)attn_bwd_dq_kernel, 65536)) return NV_ERR_LAUNCH;
         once = true;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1542,19 +1346,14 @@ static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, con
     p.kv_start = kv_start; p.cu = cu; p.B = B; p.S = S; p.Sst = Sst; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
     p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
     p.rope_cos = (const bf16_t*)rope_cos; p.rope_sin = (const bf16_t*)rope_sin;
-    p.kvacc = kvacc; p.kvacc_len = kvacc_len; p.kvacc_first = kvacc_first;
+    p.kvacc = kvacc; p.kvacc_len = kvacc_len; p.kvacc_add = kvacc_add;
     const int scap = (S + 31) & ~31;
     p.stat_cap = 8 * scap <= 12288 ? scap : 0;                // dK/dV: lse + dsum of one (sample, head) in LDS when they fit (S <= 1536)
     const int dkv_lds = 65536 + 8 * p.stat_cap;               // 4 slots x (Q, dO) x 8 KiB, then the statistics: two blocks per CU
     // with q_row_min > 0 only those query rows carry gradient: dK/dV still cover every key, dQ rows below
     // q_row_min are NOT written (the caller zero-fills them)
-    if (variant == 1) {
-        NV_LAUNCH(attn_bwd_dkv_kernel<1>, dim3(B * H, (S + 63) / 64), dim3(256), dkv_lds, st, p);
-        NV_LAUNCH(attn_bwd_dq_kernel<1>, dim3(B * H, q_row_min < 0 ? 2 : (S - q_row_min + 63) / 64), dim3(256), 65536, st, p);
-    } else {
-        NV_LAUNCH(attn_bwd_dkv_kernel<2>, dim3(B * H, (S + 127) / 128), dim3(256), dkv_lds, st, p);
-        NV_LAUNCH(attn_bwd_dq_kernel<2>, dim3(B * H, q_row_min < 0 ? 1 : (S - q_row_min + 127) / 128), dim3(256), 65536, st, p);
-    }
+    NV_LAUNCH(attn_bwd_dkv_kernel, dim3(B * H, (S + 63) / 64), dim3(256), dkv_lds, st, p);
+    NV_LAUNCH(attn_bwd_dq_kernel, dim3(B * H, q_row_min < 0 ? 2 : (S - q_row_min + 63) / 64), dim3(256), 65536, st, p);
     return nv_check_launch();
 }
 
@@ -1591,7 +1390,7 @@ int nv_attn_bwd_strided_kvacc_bf16(const void* qkv, const void* out, const void*
                                    int head_dim, int q_row_min, void* stream) {
     if (S_stride < S || !kv_acc || !prefix_len) return NV_ERR_SHAPE;
     return attn_bwd_impl(qkv, out, dout, lse2, kv_start, dqkv, workspace, B, S, H, head_dim, q_row_min, nullptr, nullptr, stream, nullptr,
-                         -1, S_stride, kv_acc, prefix_len, first);
+                         -1, S_stride, kv_acc, prefix_len, first ? 0 : 1);
 }
 
 // backward over packed rows (see nv_attn_fwd_varlen_bf16); rope_cos/rope_sin optional (both or neither); `rows` = cu[B]

@@ -32,7 +32,5 @@ dqkv = torch.empty_like(qkv)
 fl = 4.0 * B * H * S * S * hd / 2
 t = bench(lambda: ops.attn_fwd(qkv, kvs, B, S, H, hd, out=o, lse2=lse))
 print(f"attn_fwd               {t:7.1f} us  {fl / t / 1e6:6.0f} TF")
-for var in ("1", "2"):
-    os.environ["NV_ATTN_BWD_VARIANT"] = var
-    t = bench(lambda: ops.attn_bwd(qkv, o, do, lse, kvs, B, S, H, hd, dqkv=dqkv))
-    print(f"attn_bwd variant {var}     {t:7.1f} us  {2.5 * fl / t / 1e6:6.0f} TF   (prep + dK/dV + dQ)")
+t = bench(lambda: ops.attn_bwd(qkv, o, do, lse, kvs, B, S, H, hd, dqkv=dqkv))
+print(f"attn_bwd               {t:7.1f} us  {2.5 * fl / t / 1e6:6.0f} TF   (prep + dK/dV + dQ)")
