@@ -34,7 +34,17 @@ extern "C" {
  *   epilogue 0 store | 1 C = bf16(C + bf16(acc))  (grad accumulation)
  *            2 C = bf16(R[m,n] + bf16(acc))       (residual add)   | 3 C = bf16(acc + R[n]) (bias)
  *   tile_cfg 0 planned per shape | 1 128x128 | 8 256x256 | 84..88 the 256-wide tile cut off after 4..8 fragment rows per wave
- *   (128 / 160 / 192 / 224 / 256 x 256; forward and dgrad layouts).   lda/ldb multiples of 8, A/B 16-B aligned. */
+ *   (128 / 160 / 192 / 224 / 256 x 256; forward and dgrad layouts).   lda/ldb multiples of 8, A/B 16-B aligned.
+ *   C and R: any N, ldc and ldr, 2-byte alignment.  The fast (staged, 16-byte) store path needs N % 8 == 0, ldc % 8 == 0,
+ *   ldr % 8 == 0 and 16-byte aligned C and R; anything else is stored element by element.  Only [0, M) x [0, N) of C is written
+ *   (epilogue 4, the SwiGLU backward of the NN layout: [0, M) x [0, 2N), with R = gate|up [M, 2N]).
+ *   K == 0 is the empty sum: epilogue 0 writes zeros, 1 leaves bf16(C), 2 writes bf16(R), 3 writes bf16(R[n]); A and B are not read.
+ *   M == 0 or N == 0 returns NV_OK and touches nothing.
+ *   Refusals, all before any launch.  NV_ERR_ARG: a NULL A, B or C, a negative size, R == NULL for an epilogue that reads it
+ *   (2, 3, 4, 5), an unknown layout, tile_cfg or epilogue, epilogue 4 outside NN, epilogue 5 outside NT or through
+ *   nv_gemm_bf16 / nv_gemm_bf16_ws.  NV_ERR_SHAPE: K % 64 != 0 in layouts 0 and 1, lda or ldb not a multiple of 8, A or B off
+ *   16 bytes, and an A or B operand that spans more than 4 GiB - 1 bytes from its base ((rows - 1) * ld + cols elements: the
+ *   hardware bounds check of the operand loads is a 32-bit byte count; such a span is refused, never clamped). */
 int nv_gemm_bf16(int layout, const void* A, const void* B, void* C, const void* R, int M, int N, int K, int lda,
                  int ldb, int ldc, int ldr, int epilogue, int tile_cfg, void* stream);
 
@@ -51,7 +61,8 @@ int nv_gemv_bf16(const void* A, const void* W, void* C, const void* R, int M, in
 /*   packed q|k|v projection with RoPE (modified_lm.py:112-116 -> HF LlamaAttention) applied to the first rope_cols
  *   columns in the GEMM epilogue: position of row m = pos[m] (int32, packed rows) or, with pos == NULL, m % S; tables as
  *   nv_rope_bf16. Bit-identical to
- *   nv_gemm_bf16(NT) + nv_rope_bf16. */
+ *   nv_gemm_bf16(NT) + nv_rope_bf16.  NV_ERR_ARG: NULL tables, pos == NULL with S <= 0, rope_cols < 0, > N or not a multiple of
+ *   128; NV_ERR_SHAPE: N % 8, ldc % 8, C or a table off 16 bytes (this epilogue has the staged store path only); then as nv_gemm_bf16. */
 int nv_gemm_bf16_rope(const void* A, const void* W, void* C, const void* rope_cos, const void* rope_sin, const int* pos, int M,
                       int N, int K, int lda, int ldw, int ldc, int S, int rope_cols, void* workspace, void* stream);
 /*   the same with an explicit tile configuration (nv_gemm_bf16_ws's `tile_cfg`: 0 planned, 8 = 256x256, 84..88 = the 256-wide tile
@@ -77,7 +88,10 @@ int nv_gemv_fp8w(const void* A, const void* Wq, const float* scales, void* C, co
  *   other shape returns NV_ERR_SHAPE (-2) and the caller runs nv_fp8_dequant_rows + nv_gemm_bf16.  mode: 0 = default, 7 = operand
  *   bf16(s*q) bit for bit as nv_fp8_dequant_rows writes it, 9 = v_cvt_scalef32_pk_bf16_fp8 unscaled + s[n] on the fp32 accumulator
  *   (one bf16 rounding per weight less than the reference-on-de-quantised-weights semantics); 8 = the same instruction with s as its
- *   scale operand: a measurement only -- the hardware uses the operand's exponent alone, the results are WRONG by up to 2x.  tile_cfg 0 | 84 | 85; epilogue 0 (store) | 2 (residual); K % 64 == 0, ldq % 16 == 0; workspace as nv_gemm_bf16_ws */
+ *   scale operand: a measurement only -- the hardware uses the operand's exponent alone, the results are WRONG by up to 2x.  tile_cfg 0 | 84 | 85; epilogue 0 (store) | 2 (residual); K % 64 == 0, ldq % 16 == 0; workspace as nv_gemm_bf16_ws.
+ *   NV_ERR_ARG: a NULL A, codes, scales or C, a negative size, K <= 0, another epilogue, mode or tile_cfg, R == NULL with epilogue 2;
+ *   NV_ERR_SHAPE: K % 64, lda % 8, ldq % 16, A, codes or scales off 16 bytes, an operand span above 4 GiB - 1 bytes, and (tile_cfg 0) a
+ *   shape the pre-pass form serves better.  C and R as nv_gemm_bf16. */
 int nv_gemm_fp8w(const void* A, const void* codes, const float* scales, void* C, const void* R, int M, int N, int K, int lda, int ldq,
                  int ldc, int ldr, int epilogue, int mode, int tile_cfg, void* workspace, void* stream);
 /*   process-wide default for mode = 0 (7 | 9; 0 = query only); returns the previous default */

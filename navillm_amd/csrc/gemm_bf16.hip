@@ -1424,12 +1424,19 @@ int dispatch_epi(const GemmArgs& p, int epi, int tile_cfg, hipStream_t st) {
     return NV_ERR_ARG;
 }
 
-inline uint32_t span_bytes(long rows, long cols, long ld) {
-    if (rows <= 0) return 0;
+// Bytes of an operand addressable from its base: the num_records of its buffer descriptor, a 32-bit field.  An empty operand
+// (K == 0) spans nothing: every load of it is out of range and reads as zero.  A span that does not fit is NOT clamped (the rows
+// beyond 4 GiB would read as zero and the result would be wrong without an error): set_spans() refuses it.
+inline long span_bytes(long rows, long cols, long ld) {
+    if (rows <= 0 || cols <= 0) return 0;
     // bounds are checked per dword: round the last row up to an even element count (ld % 8 == 0
     // guarantees that extra element still lies inside the row)
-    const long b = ((rows - 1) * ld + ((cols + 1) & ~1L)) * 2;
-    return b > 0xffffffffL ? 0xffffffffu : (uint32_t)b;
+    return ((rows - 1) * ld + ((cols + 1) & ~1L)) * 2;
+}
+inline bool set_spans(GemmArgs& p, long a, long b) {
+    if (a < 0 || b < 0 || a > 0xffffffffL || b > 0xffffffffL) return false;
+    p.a_bytes = (uint32_t)a; p.b_bytes = (uint32_t)b;
+    return true;
 }
 
 }  // namespace
@@ -1477,14 +1484,14 @@ static int gemm_entry(int layout, const void* A, const void* B, void* C, const v
     switch (layout) {
         case 0:  // NT: A[M,K], B[N,K]
             if (K % 64) return NV_ERR_SHAPE;
-            p.a_bytes = span_bytes(M, K, lda); p.b_bytes = span_bytes(N, K, ldb);
+            if (!set_spans(p, span_bytes(M, K, lda), span_bytes(N, K, ldb))) return NV_ERR_SHAPE;
             return dispatch_epi<true, true>(p, epilogue, tile_cfg, st);
         case 1:  // NN: A[M,K], B[K,N]
             if (K % 64) return NV_ERR_SHAPE;
-            p.a_bytes = span_bytes(M, K, lda); p.b_bytes = span_bytes(K, N, ldb);
+            if (!set_spans(p, span_bytes(M, K, lda), span_bytes(K, N, ldb))) return NV_ERR_SHAPE;
             return dispatch_epi<true, false>(p, epilogue, tile_cfg, st);
         case 2:  // TN: A[K,M], B[K,N]   (K = contraction, any size: OOB k-rows read as zero)
-            p.a_bytes = span_bytes(K, M, lda); p.b_bytes = span_bytes(K, N, ldb);
+            if (!set_spans(p, span_bytes(K, M, lda), span_bytes(K, N, ldb))) return NV_ERR_SHAPE;
             return dispatch_epi<false, false>(p, epilogue, tile_cfg, st);
     }
     return NV_ERR_ARG;
@@ -1545,11 +1552,7 @@ extern "C" int nv_gemm_fp8w(const void* A, const void* codes, const float* scale
     p.debug = 0; p.persist = 0; p.band_reduce = 1; p.c_nt = 1; p.group_m = 4; p.epi_preload = 1;
     p.col_strips = (long)N > (long)M ? 1 : 0;
     p.b_scales = scales; p.fp8_epi = mode == 9 ? 1 : 0;
-    p.a_bytes = span_bytes(M, K, lda);
-    {
-        const long b = (long)(N - 1) * ldq + K;                      // bytes of codes addressable from the base
-        p.b_bytes = b > 0xffffffffL ? 0xffffffffu : (uint32_t)b;
-    }
+    if (!set_spans(p, span_bytes(M, K, lda), (long)(N - 1) * ldq + K)) return NV_ERR_SHAPE;   // (bytes of codes addressable from the base)
     hipStream_t st = (hipStream_t)stream;
     const int pipe = mode == 7 ? 7 : 8;
     return epilogue == EPI_STORE ? launch_fp8<EPI_STORE>(p, tme, pipe, st) : launch_fp8<EPI_RESID>(p, tme, pipe, st);

@@ -83,8 +83,10 @@ def test_gemm_bf16_epilogues():
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("M,N,K", [(5152, 4096, 1024), (4864, 4096, 2048), (2104, 3072, 4096)])
 def test_gemm_bf16_splitk_tail(layout, M, N, K):
-    """shapes whose 256x256 tile count leaves a small partial round -> the split-K tail path (tickets, slabs);
-    repeated launches also check that the ticket words are left clean."""
+    """shapes whose 256x256 tile count leaves a partial round.  Of the three only (2104, 3072, 4096) -- 108 tiles, 64 K-tiles --
+    still takes the split-K tail path (two slices; tickets, slabs): (5152, 4096, 1024) has 80 tail tiles of 16 K-tiles and
+    (4864, 4096, 2048) 48 of 32, below the planner's 20-K-tile minimum slice, so they run unsplit.  Repeated launches also check
+    that the ticket words are left clean.  Every split count, bit for bit: tests/test_gemm_ref_gpu.py."""
     from navillm_amd import ops
     if layout == 0:
         A, B = rnd(M, K, dtype=BF, seed=15), rnd(N, K, dtype=BF, seed=16, scale=0.05)
