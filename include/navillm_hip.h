@@ -142,8 +142,8 @@ int nv_scale_dev_bf16(const void* x, void* out, long n, const float* scale_dev, 
 int nv_gather_rows_bf16(const void* src, const int* rows, void* out, int n, int d, void* stream);
 int nv_scatter_rows_bf16(const void* src, const int* rows, void* dst, int n, int d, void* stream);
 
-/* ---- K7b: causal + left-pad attention of HF LlamaAttention (head_dim 128), flash style.
- *   qkv [B*S, 3*H*128] post-RoPE, out [B*S, H*128], lse2 [B,H,S] (log2 domain, +inf for fully
+/* ---- K7b: causal + left-pad attention of HF LlamaAttention (head_dim 64 or 128; any other value: NV_ERR_SHAPE before any launch),
+ *   flash style.  qkv [B*S, 3*H*head_dim] post-RoPE, out [B*S, H*head_dim], lse2 [B,H,S] (log2 domain, +inf for fully
  *   masked rows), kv_start[b] = number of left-pad positions of sample b. */
 /*   q_row_min (multiple of 128, 0 = all): only query rows >= q_row_min of every sample are computed (forward) or
  *   carry gradient (backward; dQ rows below it are left untouched) -- the navigation modes read one row. */
@@ -154,7 +154,7 @@ int nv_attn_fwd_bf16(const void* qkv, void* out, float* lse2, const int* kv_star
 /*   ... with the cache length and the first computed query row in DEVICE memory: dyn = {S, q_row_min} (a decode step replayed
  *   from a hipGraph has frozen launch arguments); the grid covers S_stride, query blocks at or beyond S exit at once */
 /*   decode attention (one new token per sample): query r = q slice of cache row crow[r] of sample r, keys/values = cache rows
- *   r*cap + [0, pos[r]]; out [M, H*128] compact; HBM-bound streaming form, K and V read once */
+ *   r*cap + [0, pos[r]]; out [M, H*head_dim] compact; HBM-bound streaming form, K and V read once */
 int nv_attn_decode_bf16(const void* kv, const int* crow, const int* pos, void* out, int M, int H, int head_dim, int cap, void* stream);
 int nv_attn_fwd_strided_dyn_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, int B, int S_stride, int H, int head_dim,
                                  const int* dyn, void* stream);
@@ -170,7 +170,8 @@ int nv_attn_fwd_varlen_bf16(const void* qkv, void* out, float* lse2, const int* 
  *   LlamaAttention in bf16 -- scores = bf16(bf16(q k^T) * hd^-0.5), P = bf16(softmax_fp32(scores)), out = bf16(P v) -- computed in
  *   two passes.  cu == NULL: padded layout (as nv_attn_fwd_bf16), else packed rows (as nv_attn_fwd_varlen_bf16, kv_start = pos0).
  *   Used to show that the distance between the product kernel (fp32 scores, flash style) and the reference's bf16 run is this
- *   difference in rounding points and nothing else. */
+ *   difference in rounding points and nothing else.  head_dim 128 only (64 is refused with NV_ERR_SHAPE): the reference models it
+ *   is compared with are 128 wide. */
 int nv_attn_fwd_hfround_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, const int* cu, int B, int S, int H,
                              int head_dim, int q_row_min, void* stream);
 /*   backward over the K/V-cache layout of nv_attn_fwd_strided_bf16 (training with a cached prompt prefix, navillm_amd/episode.py):
@@ -192,8 +193,8 @@ int nv_attn_bwd_strided_kvacc_bf16(const void* qkv, const void* out, const void*
  *   position = prefix_len + j) and STORES the fp32 sum over the steps of the prefix rows' dK|dV in kv_acc [B*cap, 2*H*head_dim]
  *   (row b*cap + key).  workspace: (R - Mp) * H floats; at most 128 steps, at most 1536 rows per sample and step */
 /*   round 5: the FORWARD attention of all T steps of a prefix-reuse episode in one launch, reading the episode row buffers in place
- *   (no scatter into the K/V-cache layout and back): qkv [rows, 3*H*128] post-RoPE -- prefix rows of sample b at [cu[b], cu[b+1]), step
- *   t's rows of sample b at [tab[t*B+b], + tab[T*B+t*B+b]) --, out [rows, H*128] written at the steps' rows, lse_ptrs = device array of T
+ *   (no scatter into the K/V-cache layout and back): qkv [rows, 3*H*head_dim] post-RoPE -- prefix rows of sample b at [cu[b], cu[b+1]), step
+ *   t's rows of sample b at [tab[t*B+b], + tab[T*B+t*B+b]) --, out [rows, H*head_dim] written at the steps' rows, lse_ptrs = device array of T
  *   pointers to fp32 [B, H, cap] (step t's log2-domain lse at cache position prefix_len + j).  n_max = longest per-sample row count of a
  *   step.  Bit-identical to scatter + nv_attn_fwd_strided_bf16 + gather per step. */
 int nv_attn_fwd_episode_bf16(const void* qkv, void* out, const void* lse_ptrs, const int* cu, const int* tab, int T, int B, int H,

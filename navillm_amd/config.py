@@ -15,7 +15,7 @@ class NavConfig:
     # ---- causal LM (Llama family; reference: HF LlamaConfig) ----
     hidden_size: int = 4096          # d
     num_layers: int = 32             # L
-    num_heads: int = 32              # H  (head_dim = d / H, the HIP attention is built for 128)
+    num_heads: int = 32              # H  (head_dim = d / H: the HIP attention is built for 64 and 128)
     intermediate_size: int = 11008   # ff
     base_vocab_size: int = 32000     # tokenizer vocab before the 6 added tokens
     rms_norm_eps: float = 1e-6
@@ -106,6 +106,14 @@ def vicuna_7b(**over):
 def vicuna_13b(**over):
     kw = dict(hidden_size=5120, num_layers=40, num_heads=40, intermediate_size=13824,
               base_vocab_size=32000)
+    kw.update(over)
+    return NavConfig(**kw)
+
+
+def gpt2_small_shaped(**over):
+    """A GPT-2-small-shaped Llama-family LM with 64-wide heads (d = 768, 12 heads, 12 layers, ff = 3072: every GEMM rule, K % 64 and
+    N % 8, holds): the small configuration for tests and first contact at head_dim 64.  The scene encoder keeps its defaults."""
+    kw = dict(hidden_size=768, num_layers=12, num_heads=12, intermediate_size=3072, base_vocab_size=32000)
     kw.update(over)
     return NavConfig(**kw)
 

@@ -1,8 +1,9 @@
-// Causal + left-pad flash attention, forward and backward, head_dim = 128, bf16 in/out,
+// Causal + left-pad flash attention, forward and backward, head_dim = 64 or 128 (template parameter HD of every kernel and of
+// the device functions they share; the entry points dispatch on their head_dim argument), bf16 in/out,
 // fp32 softmax (K7b in SURVEY.md §2.2; reference: HF LlamaAttention reached from
 // models/modified_lm.py:112-116, eager path = softmax(QK^T*scale + mask) @ V).
 //
-// Data: packed post-RoPE qkv [B*S, 3*H*128] (q | k | v), out [B*S, H*128], positions s=0..S-1
+// Data: packed post-RoPE qkv [B*S, 3*H*HD] (q | k | v), out [B*S, H*HD], positions s=0..S-1
 // per sample, keys s < kv_start[b] are left padding (masked), causal key <= query.
 //
 // CDNA4 mapping (all three kernels share it):
@@ -12,18 +13,15 @@
 //    scalar, and P^T is already laid out as the next MFMA's B operand (k = keys, in a
 //    permuted order that the V^T operand reproduces) -- no LDS round trip for P.
 //  * K/V (or Q/dO) tiles are DMA'd HBM->LDS with bounds-checked buffer_load...lds into an
-//    XOR-swizzled [rows][128] image that serves both ds_read_b128 (row-major operand) and
-//    ds_read_b64_tr_b16 (transposed operand) conflict-free (see key4; verified with SQ_LDS_BANK_CONFLICT); double buffered.
+//    XOR-swizzled [rows][HD] image that serves both ds_read_b128 (row-major operand) and
+//    ds_read_b64_tr_b16 (transposed operand) conflict-free (see row_key; verified with SQ_LDS_BANK_CONFLICT); double buffered.
 //  * lse is kept in the log2 domain (lse2 = m2 + log2(l)); fully masked rows store +inf so
 //    the backward's exp2(s2 - lse2) is exactly 0 for them.
 #include "nv_common.h"
 
 namespace {
 
-constexpr int HD = 128;
-constexpr int ROWB = HD * 2;  // 256-B LDS rows
-
-// XOR key of a row's sixteen 16-byte slots.  A wave's ds_read_b128 is serviced in four groups of 16 lanes that are NOT the four
+// XOR key of a 256-B row's sixteen 16-byte slots (head_dim 128).  A wave's ds_read_b128 is serviced in four groups of 16 lanes that are NOT the four
 // quarters of the wave -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 (MI355X_MICROARCH.md, LDS) -- so the rows a
 // group touches in a row-major fragment read are {0-3, 12-15} with k-group g and {4-11} with k-group g ^ 1.  The key sends the
 // first set onto slots 0-7 and the second onto 8-15 (both closed under ^ 1): 16 distinct slots per group, no bank conflict.  Its upper
@@ -32,39 +30,59 @@ constexpr int ROWB = HD * 2;  // 256-B LDS rows
 // instead of 4 -- SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.31-0.40 in profiles/r03_sq_counters_prefix_episode.txt.)
 __device__ __forceinline__ int key4(int row) { return (((row & 7) ^ ((row & 8) >> 1)) << 1) | ((row >> 3) & 1); }
 
-// DMA `ROWS` rows x 128 bf16 (global row stride ld elements) into an LDS image.
-template <int ROWS, int NT>
+// XOR key of a 128-B row's eight 16-byte slots (head_dim 64).  Two rows share a 256-B bank line: row r, physical slot p sits at
+// 16-byte bank position (r & 1) * 8 + p, so rows of equal parity compete for the same eight positions.  A service group of a
+// row-major fragment read (above) holds eight rows of each parity: {0, 2, 12, 14} with k-group g and {4, 6, 8, 10} with g ^ 1 (and the
+// same + 1).  With key = row & 6 the first set's keys are {0, 2, 4, 6} and the second's {4, 6, 0, 2}; the logical slot c = kk*4 + g
+// resp. c ^ 1 turns them into c ^ {0, 2, 4, 6} and c ^ {5, 7, 1, 3}: eight distinct positions per parity, sixteen per group, no
+// conflict.  The transposing read takes 8 aligned rows x 32 B per half-wave: four rows of each parity, whose key bits 1-2 =
+// (row >> 1) & 3 are distinct, so the eight 32-B pairs land on the eight pair positions of the bank line.  Bit 0 of the key is 0:
+// a row's two slots of a 32-B pair stay in place, as frag_tr expects.
+__device__ __forceinline__ int key3(int row) { return row & 6; }
+
+template <int HD>
+__device__ __forceinline__ int row_key(int row) {
+    static_assert(HD == 64 || HD == 128, "head_dim 64 or 128");
+    if constexpr (HD == 128) return key4(row); else return key3(row);
+}
+
+// DMA `ROWS` rows x HD bf16 (global row stride ld elements) into an LDS image.
+template <int HD, int ROWS, int NT>
 __device__ __forceinline__ void stage_rows(const u32x4& rsrc, LDS_PTR(char) lds_p, int row0, int col0, int ld,
                                            int tid) {
+    constexpr int ROWB = HD * 2, SLOTS = HD / 8, RPC = 1024 / ROWB;   // LDS row bytes, 16-byte slots per row, rows per 1-KiB chunk
     const uint32_t lds = lds_addr_of(lds_p);
     constexpr int ITERS = (ROWS * ROWB) / (NT * 16);
     static_assert((ROWS * ROWB) % (NT * 16) == 0, "tile/threads mismatch");
     const int wave = tid >> 6, lane = tid & 63;
 #pragma unroll
     for (int it = 0; it < ITERS; ++it) {
-        const int chunk = it * (NT / 64) + wave;      // 1 KiB = 4 rows
-        const int row = chunk * 4 + (lane >> 4);
-        const int slot = (lane & 15) ^ key4(row);
+        const int chunk = it * (NT / 64) + wave;      // 1 KiB = 4 rows of 256 B or 8 rows of 128 B
+        const int row = chunk * RPC + (lane >> (HD == 128 ? 4 : 3));
+        const int slot = (lane & (SLOTS - 1)) ^ row_key<HD>(row);
         const uint32_t voff = (uint32_t)(((long)(row0 + row) * ld + col0 + slot * 8) * 2);
         dma16(rsrc, __builtin_amdgcn_readfirstlane(lds + chunk * 1024), voff);
     }
 }
 
 // row-major operand fragment: lane (idx=lane&15, kg=lane>>4) <- tile[r0+idx][kk*32+kg*8 .. +7]
+template <int HD>
 __device__ __forceinline__ bf16x8 frag_rm(LDS_PTR(char) tile, int r0, int kk, int lane) {
     const int row = r0 + (lane & 15);
-    const int slot = (kk * 4 + (lane >> 4)) ^ key4(row);
-    return *(LDS_PTR(bf16x8))(tile + row * ROWB + slot * 16);
+    const int slot = (kk * 4 + (lane >> 4)) ^ row_key<HD>(row);
+    return *(LDS_PTR(bf16x8))(tile + row * (HD * 2) + slot * 16);
 }
 
 // transposed operand fragment: lane (idx, kg) <- { tile[rA+kg*4+e][c0+idx] , tile[rB+kg*4+e][c0+idx] } e=0..3
+template <int HD>
 __device__ __forceinline__ bf16x8 frag_tr(LDS_PTR(char) tile, int rA, int rB, int c0, int lane) {
+    constexpr int ROWB = HD * 2;
     const int t = lane & 15, kg = lane >> 4;
     const int slot = (c0 >> 3) + ((t & 3) >> 1);
     const int half = (t & 1) * 8;
     const int ra = rA + kg * 4 + (t >> 2), rb = rB + kg * 4 + (t >> 2);
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + ra * ROWB + ((slot ^ key4(ra)) << 4) + half));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + rb * ROWB + ((slot ^ key4(rb)) << 4) + half));
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + ra * ROWB + ((slot ^ row_key<HD>(ra)) << 4) + half));
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))(tile + rb * ROWB + ((slot ^ row_key<HD>(rb)) << 4) + half));
     s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -82,10 +100,13 @@ __device__ __forceinline__ bf16x8 pack_frag(const f32x4& a, const f32x4& b) {
 template <typename V>
 __device__ __forceinline__ void pin(V& v) { asm volatile("" : "+v"(v)); }
 
-// dK/dV kernels: a 4-slot ring of (Q, dO) tiles, up to three tile prefetches (4 DMA instructions per thread each) in flight
+// dK/dV kernels: a 4-slot ring of (Q, dO) tiles, up to three tile prefetches (HD/32 DMA instructions per thread each: 4 at
+// head_dim 128, 2 at 64) in flight
 constexpr int DKV_SLOTS = 4;
+template <int HD>
 __device__ __forceinline__ void wait_stages(int still_in_flight) {
-    if (still_in_flight >= 2) wait_vmcnt<8>(); else if (still_in_flight == 1) wait_vmcnt<4>(); else wait_vmcnt<0>();
+    constexpr int PER = HD / 32;
+    if (still_in_flight >= 2) wait_vmcnt<2 * PER>(); else if (still_in_flight == 1) wait_vmcnt<PER>(); else wait_vmcnt<0>();
 }
 
 // 2^x as the bare v_exp_f32: exp2f() wraps it in a denormal-range fix-up (compare, select, add, ldexp: 7 VALU ops per
@@ -104,19 +125,21 @@ __device__ __forceinline__ float grp_sum(float v) {
 
 // store one gradient row fragment set (lane: 4 consecutive d per 16-wide tile dt, d = dt*16 + g*4 + r) as bf16, optionally
 // through the transpose of RoPE.  Bit-identical to "round to bf16, then nv_rope_bf16(backward=1)": the partner of
-// d < 64 is d + 64 = tile dt + 4 of the SAME lane.
-__device__ __forceinline__ void store_grad_row(bf16_t* dst, const f32x4 (&v)[8], float scale, const bf16_t* cos_row,
+// d < HD/2 is d + HD/2 = tile dt + HD/32 of the SAME lane (dt + 4 at head_dim 128, dt + 2 at 64).
+template <int HD>
+__device__ __forceinline__ void store_grad_row(bf16_t* dst, const f32x4 (&v)[HD / 16], float scale, const bf16_t* cos_row,
                                                const bf16_t* sin_row) {
+    constexpr int HT = HD / 32;   // 16-wide tiles per rotate-half
     if (!cos_row) {
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
+        for (int dt = 0; dt < HD / 16; ++dt) {
             u32x2 w = {pack2bf(v[dt][0] * scale, v[dt][1] * scale), pack2bf(v[dt][2] * scale, v[dt][3] * scale)};
             *(u32x2*)(dst + dt * 16) = w;
         }
         return;
     }
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < HT; ++dt) {
         const u32x2 cw = *(const u32x2*)(cos_row + dt * 16), sw = *(const u32x2*)(sin_row + dt * 16);
         const float c[4] = {__uint_as_float(cw[0] << 16), __uint_as_float(cw[0] & 0xffff0000u), __uint_as_float(cw[1] << 16),
                             __uint_as_float(cw[1] & 0xffff0000u)};
@@ -125,12 +148,12 @@ __device__ __forceinline__ void store_grad_row(bf16_t* dst, const f32x4 (&v)[8],
         float o1[4], o2[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float x1 = rbf(v[dt][r] * scale), x2 = rbf(v[dt + 4][r] * scale);
+            const float x1 = rbf(v[dt][r] * scale), x2 = rbf(v[dt + HT][r] * scale);
             o1[r] = rbf(x1 * c[r]) + rbf(x2 * sn[r]);
             o2[r] = rbf(x2 * c[r]) + rbf(-x1 * sn[r]);
         }
         *(u32x2*)(dst + dt * 16) = u32x2{pack2bf(o1[0], o1[1]), pack2bf(o1[2], o1[3])};
-        *(u32x2*)(dst + (dt + 4) * 16) = u32x2{pack2bf(o2[0], o2[1]), pack2bf(o2[2], o2[3])};
+        *(u32x2*)(dst + (dt + HT) * 16) = u32x2{pack2bf(o2[0], o2[1]), pack2bf(o2[2], o2[3])};
     }
 }
 
@@ -181,15 +204,19 @@ __device__ __forceinline__ int lse_stride(const AttnArgs& p) { return p.cu ? p.S
 // lane (ks = lane>>4, dp = lane&15) holding 8 of the 128 dims of key ks.  q.k is 8 FMAs + a 16-lane butterfly, the softmax is
 // online per lane group (fp32 scores and probabilities), p.V 8 FMAs; the 64 groups' (m, l, acc) meet in LDS.  K and V of the
 // cache are read exactly once: 2 * L * 256 B per (sample, head).
+// head_dim 64: a key is 8 lanes (LPK), a wave instruction covers 8 keys of 128 B (KPW), the butterfly has three steps and 128
+// groups meet in LDS; the partial sums take 33 KB at either width.
 constexpr int DEC_WAVES = 16, DEC_U = 4;
+template <int HD>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_t* __restrict__ kv, const int* __restrict__ crow,
                                                                     const int* __restrict__ pos, bf16_t* __restrict__ out, int H, int cap,
                                                                     float scale2) {
-    __shared__ float pm[DEC_WAVES * 4], pl[DEC_WAVES * 4];
-    __shared__ float pacc[DEC_WAVES * 4][HD + 1];
+    constexpr int LPK = HD / 8, KPW = 64 / LPK, NG = DEC_WAVES * KPW;   // lanes per key, keys per wave instruction, lane groups
+    __shared__ float pm[NG], pl[NG];
+    __shared__ float pacc[NG][HD + 1];
     const int h = blockIdx.x, r = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ks = lane >> 4, dp = lane & 15;
+    const int ks = lane >> (HD == 128 ? 4 : 3), dp = lane & (LPK - 1);
     const int ld = 3 * H * HD;
     const int L = min(pos[r] + 1, cap);                            // keys 0 .. pos (causal, left-aligned cache)
     const bf16_t* base = kv + (long)r * cap * ld;
@@ -201,18 +228,18 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_
     }
     const int kcol = H * HD + h * HD + dp * 8, vcol = 2 * H * HD + h * HD + dp * 8;
     float m = -INFINITY, l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k0 = wave * 4 + ks; k0 < L; k0 += 64 * DEC_U) {           // a 16-lane group shares k0: its lanes leave the loop together
+    for (int k0 = wave * KPW + ks; k0 < L; k0 += NG * DEC_U) {         // a lane group shares k0: its lanes leave the loop together
         u32x4 kf[DEC_U], vf[DEC_U];
 #pragma unroll
         for (int u = 0; u < DEC_U; ++u) {
-            const int key = k0 + u * 64;
+            const int key = k0 + u * NG;
             const long row = key < L ? key : L - 1;
             kf[u] = __builtin_nontemporal_load((const u32x4*)(base + row * ld + kcol));
             vf[u] = __builtin_nontemporal_load((const u32x4*)(base + row * ld + vcol));
         }
 #pragma unroll
         for (int u = 0; u < DEC_U; ++u) {
-            const int key = k0 + u * 64;
+            const int key = k0 + u * NG;
             float s = 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -222,8 +249,8 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_
             s += __shfl_xor(s, 1, 64);
             s += __shfl_xor(s, 2, 64);
             s += __shfl_xor(s, 4, 64);
-            s += __shfl_xor(s, 8, 64);
-            if (key < L) {                                          // uniform within the 16-lane group
+            if constexpr (LPK == 16) s += __shfl_xor(s, 8, 64);
+            if (key < L) {                                          // uniform within the lane group
                 const float mn = fmaxf(m, s);
                 const float sc = fast_exp2(m - mn), p = fast_exp2(s - mn);   // m = -inf the first time: exp2(-inf) = 0
                 l = l * sc + p;
@@ -236,16 +263,16 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_
             }
         }
     }
-    const int g = wave * 4 + ks;
+    const int g = wave * KPW + ks;
     if (dp == 0) { pm[g] = m; pl[g] = l; }
 #pragma unroll
     for (int j = 0; j < 8; ++j) pacc[g][dp * 8 + j] = acc[j];
     __syncthreads();
     if (tid < HD) {
         float mm = -INFINITY;
-        for (int i = 0; i < DEC_WAVES * 4; ++i) mm = fmaxf(mm, pm[i]);
+        for (int i = 0; i < NG; ++i) mm = fmaxf(mm, pm[i]);
         float num = 0.f, den = 0.f;
-        for (int i = 0; i < DEC_WAVES * 4; ++i) {
+        for (int i = 0; i < NG; ++i) {
             if (pm[i] != -INFINITY) {
                 const float w = fast_exp2(pm[i] - mm);
                 num += pacc[i][tid] * w;
@@ -263,32 +290,34 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(const bf16_
 // the tile is masked, and key_ok is not evaluated -- most tiles of a long prompt.
 
 // S^T = K Q^T : 4 key tiles x 2 query tiles
-__device__ __forceinline__ void fwd_scores(f32x4 (&s)[4][2], LDS_PTR(char) sk, const bf16x8 (&qf)[2][4], int lane) {
+template <int HD>
+__device__ __forceinline__ void fwd_scores(f32x4 (&s)[4][2], LDS_PTR(char) sk, const bf16x8 (&qf)[2][HD / 32], int lane) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) s[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
+    for (int kk = 0; kk < HD / 32; ++kk) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const bf16x8 kf = frag_rm(sk, i * 16, kk, lane);
+            const bf16x8 kf = frag_rm<HD>(sk, i * 16, kk, lane);
 #pragma unroll
             for (int j = 0; j < 2; ++j) s[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[j][kk], s[i][j], 0, 0, 0);
         }
     }
 }
 
-// O^T += V^T P^T : k = keys (two 32-key steps), 8 d tiles
-__device__ __forceinline__ void fwd_pv(f32x4 (&o)[8][2], const f32x4 (&s)[4][2], LDS_PTR(char) sv, int lane) {
+// O^T += V^T P^T : k = keys (two 32-key steps), HD/16 d tiles
+template <int HD>
+__device__ __forceinline__ void fwd_pv(f32x4 (&o)[HD / 16][2], const f32x4 (&s)[4][2], LDS_PTR(char) sv, int lane) {
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
         bf16x8 pf[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j) pf[j] = pack_frag(s[2 * a][j], s[2 * a + 1][j]);
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) {
-            const bf16x8 vf = frag_tr(sv, a * 32, a * 32 + 16, dt * 16, lane);
+        for (int dt = 0; dt < HD / 16; ++dt) {
+            const bf16x8 vf = frag_tr<HD>(sv, a * 32, a * 32 + 16, dt * 16, lane);
 #pragma unroll
             for (int j = 0; j < 2; ++j) o[dt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[j], o[dt][j], 0, 0, 0);
         }
@@ -296,12 +325,12 @@ __device__ __forceinline__ void fwd_pv(f32x4 (&o)[8][2], const f32x4 (&s)[4][2],
 }
 
 // scores, mask + online softmax of m2 / l / o (per query = per lane&15), P V
-template <class KeyOk>
-__device__ __forceinline__ void fwd_tile(f32x4 (&o)[8][2], float (&m2)[2], float (&l)[2], LDS_PTR(char) sk, LDS_PTR(char) sv,
-                                         const bf16x8 (&qf)[2][4], int key0, bool interior, KeyOk key_ok, float scale2, int lane) {
+template <int HD, class KeyOk>
+__device__ __forceinline__ void fwd_tile(f32x4 (&o)[HD / 16][2], float (&m2)[2], float (&l)[2], LDS_PTR(char) sk, LDS_PTR(char) sv,
+                                         const bf16x8 (&qf)[2][HD / 32], int key0, bool interior, KeyOk key_ok, float scale2, int lane) {
     const int g = lane >> 4;
     f32x4 s[4][2];
-    fwd_scores(s, sk, qf, lane);
+    fwd_scores<HD>(s, sk, qf, lane);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         float mx = -INFINITY;                          // max of the RAW scores (scale2 > 0 commutes with max)
@@ -336,20 +365,21 @@ __device__ __forceinline__ void fwd_tile(f32x4 (&o)[8][2], float (&m2)[2], float
             }
         l[j] = l[j] * alpha + rs_;
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) o[dt][j] *= alpha;
+        for (int dt = 0; dt < HD / 16; ++dt) o[dt][j] *= alpha;
     }
-    fwd_pv(o, s, sv, lane);
+    fwd_pv<HD>(o, s, sv, lane);
 }
 
 // query tile j's output row, normalised, and its lse2 (+inf: a fully masked row) to op (the lane's 4 columns) / lse, if valid.
 // normalised: P was divided by the row sum before the PV product (HFR).  Every lane of the wave takes part in the row sum.
-__device__ __forceinline__ void fwd_store(const f32x4 (&o)[8][2], float m2, float l, int j, bool valid, bool normalised, bf16_t* op,
+template <int HD>
+__device__ __forceinline__ void fwd_store(const f32x4 (&o)[HD / 16][2], float m2, float l, int j, bool valid, bool normalised, bf16_t* op,
                                           float* lse, int lane) {
     const float lt = grp_sum(l);
     const float inv = normalised ? (lt > 0.f ? 1.f : 0.f) : (lt > 0.f ? 1.f / lt : 0.f);
     if (!valid) return;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
+    for (int dt = 0; dt < HD / 16; ++dt) {
         u32x2 w = {pack2bf(o[dt][j][0] * inv, o[dt][j][1] * inv), pack2bf(o[dt][j][2] * inv, o[dt][j][3] * inv)};
         *(u32x2*)(op + dt * 16) = w;
     }
@@ -365,11 +395,11 @@ __device__ __forceinline__ void fwd_store(const f32x4 (&o)[8][2], float m2, floa
 // which needs the row's final max and sum before P can be rounded -> two passes over the key tiles (pass 0: statistics,
 // pass 1: normalised bf16 P and the PV product).  tests/test_round2_gpu.py uses it to show that the ~1e-2 distance
 // between the product kernel and the reference's bf16 run is exactly this difference in rounding points.
-template <bool HFR>
+template <int HD, bool HFR>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 64 * ROWB;  // 16 KiB per K or V tile
+    constexpr int TILE = 64 * HD * 2;  // 16 KiB (head_dim 128) or 8 KiB (64) per K or V tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // grid (B*H, query blocks): x walks the heads, y the query blocks from the LAST one down -- causal work grows with the
     // query index, so the long blocks are dispatched first and the short ones fill the tail of the launch
@@ -386,7 +416,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
     const int kcol = p.H * HD + h * HD, vcol = 2 * p.H * HD + h * HD;
 
     // Q fragments (B operand: j = query, k = head dim), straight from HBM
-    bf16x8 qf[2][4];
+    bf16x8 qf[2][HD / 32];
     int qpos[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -394,12 +424,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
         const int ql = qpos[j] < S ? qpos[j] : S - 1;
         const bf16_t* qp = base + (long)ql * ld + h * HD + g * 8;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *(const bf16x8*)(qp + kk * 32);
+        for (int kk = 0; kk < HD / 32; ++kk) qf[j][kk] = *(const bf16x8*)(qp + kk * 32);
     }
 
-    f32x4 o[8][2];
+    f32x4 o[HD / 16][2];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
+    for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
         for (int j = 0; j < 2; ++j) o[dt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m2[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
@@ -409,8 +439,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
     const int kt_beg = kvs / 64, kt_end = q_hi / 64;           // inclusive key-tile range
     if (kt_beg <= kt_end) {
         auto stage = [&](int kt, int buf) {
-            stage_rows<64, 256>(rs, smem + buf * 2 * TILE, kt * 64, kcol, ld, tid);
-            stage_rows<64, 256>(rs, smem + buf * 2 * TILE + TILE, kt * 64, vcol, ld, tid);
+            stage_rows<HD, 64, 256>(rs, smem + buf * 2 * TILE, kt * 64, kcol, ld, tid);
+            stage_rows<HD, 64, 256>(rs, smem + buf * 2 * TILE + TILE, kt * 64, vcol, ld, tid);
         };
         float hf_inv[2] = {0.f, 0.f};
 #pragma unroll 1
@@ -426,7 +456,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) pin(qf[j][kk]);
+            for (int kk = 0; kk < HD / 32; ++kk) pin(qf[j][kk]);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         int cur = 0;
@@ -437,10 +467,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
             if constexpr (!HFR) {
                 // key tiles entirely below this wave's first query and at/after the left padding
                 const bool interior = (kt * 64 + 63 <= q0 + wave * 32) && (kt * 64 >= kvs);
-                fwd_tile(o, m2, l, sk, sv, qf, kt * 64, interior, key_ok, p.scale2, lane);
+                fwd_tile<HD>(o, m2, l, sk, sv, qf, kt * 64, interior, key_ok, p.scale2, lane);
             } else {
                 f32x4 s[4][2];
-                fwd_scores(s, sk, qf, lane);
+                fwd_scores<HD>(s, sk, qf, lane);
                 constexpr float LOG2E = 1.4426950408889634f;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -474,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
                             for (int r = 0; r < 4; ++r) s[i][j][r] = fast_exp2(s[i][j][r] - msafe) * hf_inv[j];   // normalised P (bf16 in pack_frag)
                     }
                 }
-                if (pass == 1) fwd_pv(o, s, sv, lane);
+                if (pass == 1) fwd_pv<HD>(o, s, sv, lane);
             }
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
@@ -484,7 +514,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnArgs p) {
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-        fwd_store(o, m2[j], l[j], j, qpos[j] < S, HFR, p.out + (sq.row0 + qpos[j]) * (p.H * HD) + h * HD + g * 4,
+        fwd_store<HD>(o, m2[j], l[j], j, qpos[j] < S, HFR, p.out + (sq.row0 + qpos[j]) * (p.H * HD) + h * HD + g * 4,
                   p.lse2 + ((long)b * p.H + h) * lse_stride(p) + qpos[j], lane);
 }
 
@@ -507,10 +537,11 @@ struct EpiFwdArgs {
     float scale2;
 };
 
+template <int HD>
 __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 64 * ROWB;
+    constexpr int TILE = 64 * HD * 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
     // y walks the (step, query block) pairs with the LAST query block of every step first (the longest key ranges)
@@ -526,7 +557,7 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
     const int kcol = p.H * HD + h * HD, vcol = 2 * p.H * HD + h * HD;
     const int Sv = lp + n;                                     // virtual sequence length of (sample, step)
 
-    bf16x8 qf[2][4];
+    bf16x8 qf[2][HD / 32];
     int qpos[2];                                               // VIRTUAL positions of this lane's two queries
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -535,11 +566,11 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
         const long row = off + (jl < n ? jl : n - 1);
         const bf16_t* qp = p.qkv + row * ld + h * HD + g * 8;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) qf[j][kk] = *(const bf16x8*)(qp + kk * 32);
+        for (int kk = 0; kk < HD / 32; ++kk) qf[j][kk] = *(const bf16x8*)(qp + kk * 32);
     }
-    f32x4 o[8][2];
+    f32x4 o[HD / 16][2];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
+    for (int dt = 0; dt < HD / 16; ++dt)
 #pragma unroll
         for (int j = 0; j < 2; ++j) o[dt][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m2[2] = {-INFINITY, -INFINITY}, l[2] = {0.f, 0.f};
@@ -550,14 +581,15 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
     // lie behind every query of the block and are masked)
     auto stage = [&](int kt, int buf) {
         const uint32_t lk = lds_addr_of(smem + buf * 2 * TILE), lv = lk + TILE;
+        constexpr int SLOTS = HD / 8, RPC = 1024 / (HD * 2);   // as in stage_rows
 #pragma unroll
-        for (int it = 0; it < 4; ++it) {
+        for (int it = 0; it < TILE / 4096; ++it) {
             const int chunk = it * 4 + wave;
-            const int row = chunk * 4 + (lane >> 4);
+            const int row = chunk * RPC + (lane >> (HD == 128 ? 4 : 3));
             int vk = kt * 64 + row;
             vk = vk < Sv ? vk : Sv - 1;
             const long prow = vk < lp ? (long)cub + vk : (long)off + (vk - lp);
-            const int slot = (lane & 15) ^ key4(row);
+            const int slot = (lane & (SLOTS - 1)) ^ row_key<HD>(row);
             const uint32_t vo = (uint32_t)((prow * ld + slot * 8) * 2);
             dma16(rs, __builtin_amdgcn_readfirstlane(lk + chunk * 1024), vo + (uint32_t)(kcol * 2));
             dma16(rs, __builtin_amdgcn_readfirstlane(lv + chunk * 1024), vo + (uint32_t)(vcol * 2));
@@ -567,7 +599,7 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) pin(qf[j][kk]);
+        for (int kk = 0; kk < HD / 32; ++kk) pin(qf[j][kk]);
     wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     int cur = 0;
@@ -576,7 +608,7 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
         LDS_PTR(char) sk = smem + cur * 2 * TILE;
         LDS_PTR(char) sv = sk + TILE;
         const bool interior = kt * 64 + 63 <= lp + q0 + wave * 32;      // the tile lies before this wave's first (virtual) query
-        fwd_tile(o, m2, l, sk, sv, qf, kt * 64, interior, [&](int key, int j) { return key <= qpos[j]; }, p.scale2, lane);
+        fwd_tile<HD>(o, m2, l, sk, sv, qf, kt * 64, interior, [&](int key, int j) { return key <= qpos[j]; }, p.scale2, lane);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         cur ^= 1;
@@ -584,18 +616,20 @@ __global__ __launch_bounds__(256, 2) void epi_fwd_kernel(EpiFwdArgs p) {
     float* lse2 = p.lse[t] + ((long)b * p.H + h) * p.cap;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-        fwd_store(o, m2[j], l[j], j, qpos[j] - lp < n, false, p.out + ((long)off + qpos[j] - lp) * (p.H * HD) + h * HD + g * 4,
+        fwd_store<HD>(o, m2[j], l[j], j, qpos[j] - lp < n, false, p.out + ((long)off + qpos[j] - lp) * (p.H * HD) + h * HD + g * 4,
                   lse2 + qpos[j], lane);
 }
 
 // =========================================================================== backward prep
-// dsum[b,h,q] = sum_d dO[q,d] * O[q,d]   (16 lanes per (row, head): 16-B loads, 4 items per wave)
+// dsum[b,h,q] = sum_d dO[q,d] * O[q,d]   (HD/8 lanes per (row, head): 16-B loads, 4 items per wave at head_dim 128, 8 at 64)
 // rows = B*S (padded layout) or cu[B] (packed layout: the sample of a row is found by walking cu, B is small)
+template <int HD>
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ out,
                                                             float* __restrict__ dsum, const int* __restrict__ cu, long rows, int B,
                                                             int S, int H, int q_lo, int nq) {
-    const int sub = threadIdx.x & 15;
-    const long item = (long)blockIdx.x * 16 + (threadIdx.x >> 4);   // (row, head)
+    constexpr int LPI = HD / 8;                                        // lanes per item
+    const int sub = threadIdx.x & (LPI - 1);
+    const long item = (long)blockIdx.x * (256 / LPI) + (threadIdx.x >> (HD == 128 ? 4 : 3));   // (row, head)
     const bool live = item < rows * H;
     long row = live ? item / H : 0;
     const int h = live ? (int)(item % H) : 0;
@@ -617,7 +651,7 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const bf16_t* __rest
         v += __uint_as_float(av[q] << 16) * __uint_as_float(ov[q] << 16) +
              __uint_as_float(av[q] & 0xffff0000u) * __uint_as_float(ov[q] & 0xffff0000u);
 #pragma unroll
-    for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = LPI / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if (live && sub == 0) dsum[((long)bb * H + h) * S + s_] = v;
 }
 
@@ -626,9 +660,9 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(const bf16_t* __rest
 // wave's 16 keys (fragments kf, vf).  A lane holds key lane&15 and the queries q0 + j*16 + g*4 + r, whose lse2 and dsum are lq / dsq;
 // q_ok(q) = may this lane's key be seen by query q (not evaluated when interior: no pair of the tile is masked).
 //   S = Q K^T, dP = dO V^T ; P = exp2(S scale2 - lse2), dS = P (dP - dsum) ; dV^T += dO^T P, dK^T += Q^T dS
-template <class QOk>
-__device__ __forceinline__ void dkv_tile(f32x4 (&dk)[8], f32x4 (&dv)[8], LDS_PTR(char) tq, LDS_PTR(char) tdo, const bf16x8 (&kf)[4],
-                                         const bf16x8 (&vf)[4], const float (&lq)[2][4], const float (&dsq)[2][4], int q0, bool interior,
+template <int HD, class QOk>
+__device__ __forceinline__ void dkv_tile(f32x4 (&dk)[HD / 16], f32x4 (&dv)[HD / 16], LDS_PTR(char) tq, LDS_PTR(char) tdo, const bf16x8 (&kf)[HD / 32],
+                                         const bf16x8 (&vf)[HD / 32], const float (&lq)[2][4], const float (&dsq)[2][4], int q0, bool interior,
                                          QOk q_ok, float scale2, int lane) {
     const int g = lane >> 4;
     f32x4 s[2], dp[2];
@@ -638,15 +672,16 @@ __device__ __forceinline__ void dkv_tile(f32x4 (&dk)[8], f32x4 (&dv)[8], LDS_PTR
     // still in flight (second phase: four head-dim tiles at a time).  With two waves per SIMD nothing else hides the LDS
     // latency; hipcc's own schedule keeps ONE read ahead of its MFMA, and sched_barrier stops it from re-interleaving this one.
     // (All sixteen at once, plus the second phase's first half before the softmax arithmetic: 220 VGPRs and no faster.)
+    // head_dim 64 has one such pair of k-steps and one group of four head-dim tiles.
 #pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
+    for (int k2 = 0; k2 < HD / 64; ++k2) {
         bf16x8 qa[2][2], da[2][2];
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                qa[kk][j] = frag_rm(tq, j * 16, k2 * 2 + kk, lane);
-                da[kk][j] = frag_rm(tdo, j * 16, k2 * 2 + kk, lane);
+                qa[kk][j] = frag_rm<HD>(tq, j * 16, k2 * 2 + kk, lane);
+                da[kk][j] = frag_rm<HD>(tdo, j * 16, k2 * 2 + kk, lane);
             }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -681,12 +716,12 @@ __device__ __forceinline__ void dkv_tile(f32x4 (&dk)[8], f32x4 (&dv)[8], LDS_PTR
     const bf16x8 pfrag = pack_frag(pv[0], pv[1]), dsfrag = pack_frag(ds[0], ds[1]);
     // k = the 32 queries, permuted as pack_frag lays them
 #pragma unroll
-    for (int d4 = 0; d4 < 2; ++d4) {
+    for (int d4 = 0; d4 < HD / 64; ++d4) {
         bf16x8 dot_[4], qt_[4];
 #pragma unroll
         for (int dd = 0; dd < 4; ++dd) {
-            dot_[dd] = frag_tr(tdo, 0, 16, (d4 * 4 + dd) * 16, lane);
-            qt_[dd] = frag_tr(tq, 0, 16, (d4 * 4 + dd) * 16, lane);
+            dot_[dd] = frag_tr<HD>(tdo, 0, 16, (d4 * 4 + dd) * 16, lane);
+            qt_[dd] = frag_tr<HD>(tq, 0, 16, (d4 * 4 + dd) * 16, lane);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -701,10 +736,11 @@ __device__ __forceinline__ void dkv_tile(f32x4 (&dk)[8], f32x4 (&dv)[8], LDS_PTR
 // nv_kv_grad_accum_f32 did from the bf16 row in a second pass: 342 MB per layer and step at 7B/B=8).  ak = the lane's dK columns of
 // the row in the fp32 accumulator [rows, 2*H*HD], its dV columns od = H*HD floats later; same scaling as the bf16 store, no
 // rounding.  add: onto the accumulator's value, else over it.
-__device__ __forceinline__ void store_kvacc_row(float* ak, int od, const f32x4 (&dk)[8], const f32x4 (&dv)[8], float scale, int add) {
+template <int HD>
+__device__ __forceinline__ void store_kvacc_row(float* ak, int od, const f32x4 (&dk)[HD / 16], const f32x4 (&dv)[HD / 16], float scale, int add) {
     float* av = ak + od;
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
+    for (int dt = 0; dt < HD / 16; ++dt) {
         f32x4 k4 = dk[dt] * scale, v4 = dv[dt];
         if (add) { k4 += *(const f32x4*)(ak + dt * 16); v4 += *(const f32x4*)(av + dt * 16); }
         *(f32x4*)(ak + dt * 16) = k4;
@@ -713,10 +749,11 @@ __device__ __forceinline__ void store_kvacc_row(float* ak, int od, const f32x4 (
 }
 
 // grid (B*H, ceil(S/64)), 256 threads: wave w owns the 16 keys kblk + w*16 ..; walks query tiles of 32.
+template <int HD>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 32 * ROWB;  // 8 KiB per Q or dO tile
+    constexpr int TILE = 32 * HD * 2;  // 8 KiB (head_dim 128) or 4 KiB (64) per Q or dO tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;      // grid (B*H, key blocks): key block 0 (all queries) goes first
     const Seq sq = seq_of(p, b);
@@ -736,27 +773,27 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
 
     // K and V fragments (B operand: j = key, k = head dim) from HBM
     const int key = kblk + wave * 16 + ki;
-    bf16x8 kf[4], vf[4];
+    bf16x8 kf[HD / 32], vf[HD / 32];
     {
         const int kl = key < S ? key : S - 1;
         const bf16_t* kp = base + (long)kl * ld + p.H * HD + h * HD + g * 8;
         const bf16_t* vp = base + (long)kl * ld + 2 * p.H * HD + h * HD + g * 8;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
+        for (int kk = 0; kk < HD / 32; ++kk) {
             kf[kk] = *(const bf16x8*)(kp + kk * 32);
             vf[kk] = *(const bf16x8*)(vp + kk * 32);
         }
     }
-    f32x4 dv[8], dk[8];
+    f32x4 dv[HD / 16], dk[HD / 16];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int dt = 0; dt < HD / 16; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
     // queries that can see this key block: q >= kblk (causal), q >= kvs (pad queries have p=0 anyway)
     const int qt_lo = sq.qmin / 32;
     const int qt_beg = kblk / 32 > qt_lo ? kblk / 32 : qt_lo, qt_end = (S - 1) / 32;
     auto stage = [&](int qt, int buf) {
-        stage_rows<32, 256>(rq, smem + buf * 2 * TILE, qt * 32, h * HD, ld, tid);
-        stage_rows<32, 256>(rdo, smem + buf * 2 * TILE + TILE, qt * 32, h * HD, od, tid);
+        stage_rows<HD, 32, 256>(rq, smem + buf * 2 * TILE, qt * 32, h * HD, ld, tid);
+        stage_rows<HD, 32, 256>(rdo, smem + buf * 2 * TILE + TILE, qt * 32, h * HD, od, tid);
     };
     if (qt_beg <= qt_end) {
     // The softmax statistics of every query this block will meet go to LDS FIRST.  vmcnt retires in order and hipcc does not see the
@@ -779,8 +816,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
     if (qt_beg < qt_end) stage(qt_beg + 1, 1);
     if (qt_beg + 1 < qt_end) stage(qt_beg + 2, 2);
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) { pin(kf[kk]); pin(vf[kk]); }
-    wait_stages(qt_end - qt_beg);
+    for (int kk = 0; kk < HD / 32; ++kk) { pin(kf[kk]); pin(vf[kk]); }
+    wait_stages<HD>(qt_end - qt_beg);
     __builtin_amdgcn_s_barrier();
     int cur = 0;
     const int wkey_lo = kblk + wave * 16, wkey_hi = wkey_lo + 15;
@@ -808,22 +845,22 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
         LDS_PTR(char) tq = smem + cur * 2 * TILE;
         // query tiles entirely past this wave's keys, inside [0, S), with the keys past the left padding
         const bool interior = (qt * 32 >= wkey_hi) && (qt * 32 + 31 < S) && (wkey_lo >= kvs) && (wkey_hi < S);
-        dkv_tile(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, qt * 32, interior,
+        dkv_tile<HD>(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, qt * 32, interior,
                  [&](int q) { return q < S && key <= q && key >= kvs && key < S; }, p.scale2, lane);
-        wait_stages(qt_end - (qt + 1));                                     // tile qt+1 has landed (qt+2, qt+3 may be in flight)
+        wait_stages<HD>(qt_end - (qt + 1));                                     // tile qt+1 has landed (qt+2, qt+3 may be in flight)
         __builtin_amdgcn_s_barrier();
         cur = (cur + 1) & 3;
     }
     }
     if (key >= S) return;
     if (p.kvacc && key < p.kvacc_len[b]) {
-        store_kvacc_row(p.kvacc + (sq.row0 + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
+        store_kvacc_row<HD>(p.kvacc + (sq.row0 + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
         return;
     }
     bf16_t* kp = p.dqkv + (sq.row0 + key) * ld + p.H * HD + h * HD + g * 4;
-    store_grad_row(kp, dk, p.scale, p.rope_cos ? p.rope_cos + (long)(key + sq.pos0) * HD + g * 4 : nullptr,
+    store_grad_row<HD>(kp, dk, p.scale, p.rope_cos ? p.rope_cos + (long)(key + sq.pos0) * HD + g * 4 : nullptr,
                    p.rope_sin ? p.rope_sin + (long)(key + sq.pos0) * HD + g * 4 : nullptr);
-    store_grad_row(kp + p.H * HD, dv, 1.f, nullptr, nullptr);
+    store_grad_row<HD>(kp + p.H * HD, dv, 1.f, nullptr, nullptr);
 }
 
 // =========================================================================== backward dQ
@@ -831,8 +868,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnArgs p) {
 // queries (fragments qf, dof; lse2 and dsum of the lane's query).  A lane holds query lane&15 and the keys key0 + i*16 + g*4 + r;
 // key_ok(key) = may the lane's query see that key (not evaluated when interior: no pair of the tile is masked).
 //   S^T = K Q^T, dP^T = V dO^T ; dS^T = P (dP - dsum) ; dQ^T += K^T dS^T
-template <class KeyOk>
-__device__ __forceinline__ void dq_tile(f32x4 (&dq)[8], LDS_PTR(char) sk, LDS_PTR(char) sv, const bf16x8 (&qf)[4], const bf16x8 (&dof)[4],
+template <int HD, class KeyOk>
+__device__ __forceinline__ void dq_tile(f32x4 (&dq)[HD / 16], LDS_PTR(char) sk, LDS_PTR(char) sv, const bf16x8 (&qf)[HD / 32], const bf16x8 (&dof)[HD / 32],
                                         float lse, float dsq, int key0, bool interior, KeyOk key_ok, float scale2, int lane) {
     const int g = lane >> 4;
     f32x4 s[4], dp[4];
@@ -840,12 +877,12 @@ __device__ __forceinline__ void dq_tile(f32x4 (&dq)[8], LDS_PTR(char) sk, LDS_PT
     for (int i = 0; i < 4; ++i) { s[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[i] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     // one k-step's eight fragment reads back to back, then its MFMAs (see dkv_tile)
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
+    for (int kk = 0; kk < HD / 32; ++kk) {
         bf16x8 ka[4], va[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            ka[i] = frag_rm(sk, i * 16, kk, lane);
-            va[i] = frag_rm(sv, i * 16, kk, lane);
+            ka[i] = frag_rm<HD>(sk, i * 16, kk, lane);
+            va[i] = frag_rm<HD>(sv, i * 16, kk, lane);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -875,20 +912,21 @@ __device__ __forceinline__ void dq_tile(f32x4 (&dq)[8], LDS_PTR(char) sk, LDS_PT
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
         const bf16x8 dsf = pack_frag(s[2 * a], s[2 * a + 1]);
-        bf16x8 kt_[8];
+        bf16x8 kt_[HD / 16];
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) kt_[dt] = frag_tr(sk, a * 32, a * 32 + 16, dt * 16, lane);
+        for (int dt = 0; dt < HD / 16; ++dt) kt_[dt] = frag_tr<HD>(sk, a * 32, a * 32 + 16, dt * 16, lane);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int dt = 0; dt < 8; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf, dq[dt], 0, 0, 0);
+        for (int dt = 0; dt < HD / 16; ++dt) dq[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kt_[dt], dsf, dq[dt], 0, 0, 0);
     }
 }
 
 // grid (B*H, ceil((S-q_row_min)/64)), 256 threads: wave w owns 16 queries; walks key tiles of 64.
+template <int HD>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 64 * ROWB;
+    constexpr int TILE = 64 * HD * 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;      // grid (B*H, query blocks), last (longest) query block first
     const Seq sq = seq_of(p, b);
@@ -904,34 +942,34 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     const int kcol = p.H * HD + h * HD, vcol = 2 * p.H * HD + h * HD;
 
     const int q = q0 + wave * 16 + qi;
-    bf16x8 qf[4], dof[4];
+    bf16x8 qf[HD / 32], dof[HD / 32];
     float my_lse, my_ds;
     {
         const int ql = q < S ? q : S - 1;
         const bf16_t* qp = base + (long)ql * ld + h * HD + g * 8;
         const bf16_t* dp_ = p.dout + (sq.row0 + ql) * od + h * HD + g * 8;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
+        for (int kk = 0; kk < HD / 32; ++kk) {
             qf[kk] = *(const bf16x8*)(qp + kk * 32);
             dof[kk] = *(const bf16x8*)(dp_ + kk * 32);
         }
         my_lse = p.lse2[((long)b * p.H + h) * lse_stride(p) + ql];
         my_ds = p.dsum[((long)b * p.H + h) * lse_stride(p) + ql];
     }
-    f32x4 dq[8];
+    f32x4 dq[HD / 16];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < HD / 16; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int q_hi = (q0 + 63 < S - 1) ? q0 + 63 : S - 1;
     const int kt_beg = kvs / 64, kt_end = q_hi / 64;
     if (kt_beg <= kt_end) {
         auto stage = [&](int kt, int buf) {
-            stage_rows<64, 256>(rs, smem + buf * 2 * TILE, kt * 64, kcol, ld, tid);
-            stage_rows<64, 256>(rs, smem + buf * 2 * TILE + TILE, kt * 64, vcol, ld, tid);
+            stage_rows<HD, 64, 256>(rs, smem + buf * 2 * TILE, kt * 64, kcol, ld, tid);
+            stage_rows<HD, 64, 256>(rs, smem + buf * 2 * TILE + TILE, kt * 64, vcol, ld, tid);
         };
         stage(kt_beg, 0);
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) { pin(qf[kk]); pin(dof[kk]); }
+        for (int kk = 0; kk < HD / 32; ++kk) { pin(qf[kk]); pin(dof[kk]); }
         pin(my_lse); pin(my_ds);
         wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
@@ -942,7 +980,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
             LDS_PTR(char) sk = smem + cur * 2 * TILE;
             // key tiles entirely before this wave's first query, past the left padding, with all its queries < S
             const bool interior = (kt * 64 + 63 <= wq_lo) && (kt * 64 >= kvs) && (wq_lo + 15 < S);
-            dq_tile(dq, sk, sk + TILE, qf, dof, my_lse, my_ds, kt * 64, interior,
+            dq_tile<HD>(dq, sk, sk + TILE, qf, dof, my_lse, my_ds, kt * 64, interior,
                     [&](int key) { return q < S && key <= q && key >= kvs; }, p.scale2, lane);
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
@@ -951,7 +989,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnArgs p) {
     }
     if (q >= S) return;
     bf16_t* qp = p.dqkv + (sq.row0 + q) * ld + h * HD + g * 4;
-    store_grad_row(qp, dq, p.scale, p.rope_cos ? p.rope_cos + (long)(q + sq.pos0) * HD + g * 4 : nullptr,
+    store_grad_row<HD>(qp, dq, p.scale, p.rope_cos ? p.rope_cos + (long)(q + sq.pos0) * HD + g * 4 : nullptr,
                    p.rope_sin ? p.rope_sin + (long)(q + sq.pos0) * HD + g * 4 : nullptr);
 }
 
@@ -985,10 +1023,11 @@ struct EpiArgs {
     float scale2, scale;
 };
 
+template <int HD>
 __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 32 * ROWB;
+    constexpr int TILE = 32 * HD * 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
     const int T = p.T, B = p.B, ld = p.ld, od = p.H * HD;
@@ -1006,20 +1045,20 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
     if (kblk >= klen) return;
     const int ki = lane & 15, g = lane >> 4;
     const int key = kblk + wave * 16 + ki;
-    bf16x8 kf[4], vf[4];
+    bf16x8 kf[HD / 32], vf[HD / 32];
     {
         const int kl = key < klen ? key : klen - 1;
         const bf16_t* kp = p.qkv + (krow0 + kl) * ld + p.H * HD + h * HD + g * 8;
         const bf16_t* vp = kp + p.H * HD;
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
+        for (int kk = 0; kk < HD / 32; ++kk) {
             kf[kk] = *(const bf16x8*)(kp + kk * 32);
             vf[kk] = *(const bf16x8*)(vp + kk * 32);
         }
     }
-    f32x4 dv[8], dk[8];
+    f32x4 dv[HD / 16], dk[HD / 16];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+    for (int dt = 0; dt < HD / 16; ++dt) { dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
     // the step table of this sample and the steps' lse pointers, read inside the tile loop, live in LDS (see attn_bwd_dkv_kernel:
     // no compiler-visible vector-memory load may sit between the asm-issued prefetches), and so do the current step's statistics
@@ -1038,8 +1077,8 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
         const long row0 = s_off[t];
         const u32x4 rq = make_desc_u(p.qkv + row0 * ld, (uint32_t)(((long)(n - 1) * ld + 3 * p.H * HD) * 2));
         const u32x4 rdo = make_desc_u(p.dout + row0 * od, (uint32_t)(((long)(n - 1) * od + od) * 2));
-        stage_rows<32, 256>(rq, smem + slot * 2 * TILE, q * 32, h * HD, ld, tid);
-        stage_rows<32, 256>(rdo, smem + slot * 2 * TILE + TILE, q * 32, h * HD, od, tid);
+        stage_rows<HD, 32, 256>(rq, smem + slot * 2 * TILE, q * 32, h * HD, ld, tid);
+        stage_rows<HD, 32, 256>(rdo, smem + slot * 2 * TILE + TILE, q * 32, h * HD, od, tid);
     };
     int t0 = t_beg, q0 = pre ? 0 : kblk / 32;          // a step's own keys: causal, the first query tile is the one holding key kblk
     norm(t0, q0);
@@ -1054,8 +1093,8 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
         if (t1 < t_end) stage(t1, q1, 1);
         if (t2 < t_end) stage(t2, q2, 2);
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) { pin(kf[kk]); pin(vf[kk]); }
-        wait_stages((t1 < t_end) + (t2 < t_end));
+        for (int kk = 0; kk < HD / 32; ++kk) { pin(kf[kk]); pin(vf[kk]); }
+        wait_stages<HD>((t1 < t_end) + (t2 < t_end));
         __builtin_amdgcn_s_barrier();
         int cur = 0, t_stats = -1;
         const int wkey_hi = kblk + wave * 16 + 15;
@@ -1087,9 +1126,9 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
             if (more) stage(t3, q3, (cur + 3) & 3);
             LDS_PTR(char) tq = smem + cur * 2 * TILE;
             const bool interior = (q0 * 32 + 31 < n) && (pre ? wkey_hi < lp : q0 * 32 >= wkey_hi);
-            dkv_tile(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, q0 * 32, interior, [&](int q) { return q < n && (pre ? key < lp : key <= q); },
+            dkv_tile<HD>(dk, dv, tq, tq + TILE, kf, vf, lq, dsq, q0 * 32, interior, [&](int q) { return q < n && (pre ? key < lp : key <= q); },
                      p.scale2, lane);
-            wait_stages((t2 < t_end) + (more ? 1 : 0));                       // tile 1 has landed (tiles 2, 3 may be in flight)
+            wait_stages<HD>((t2 < t_end) + (more ? 1 : 0));                       // tile 1 has landed (tiles 2, 3 may be in flight)
             __builtin_amdgcn_s_barrier();
             cur = (cur + 1) & 3;
             t0 = t1; q0 = q1; t1 = t2; q1 = q2; t2 = t3; q2 = q3;
@@ -1098,21 +1137,22 @@ __global__ __launch_bounds__(256) void epi_bwd_dkv_kernel(EpiArgs p) {
     }
     if (key >= klen) return;
     if (pre) {
-        store_kvacc_row(p.kvacc + ((long)b * p.cap + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
+        store_kvacc_row<HD>(p.kvacc + ((long)b * p.cap + key) * (2L * p.H * HD) + h * HD + g * 4, od, dk, dv, p.scale, p.kvacc_add);
         return;
     }
     const int pos = lp + key < p.cap ? lp + key : p.cap - 1;
     bf16_t* kp = p.dqkv + (krow0 + key) * ld + p.H * HD + h * HD + g * 4;
-    store_grad_row(kp, dk, p.scale, p.rope_cos ? p.rope_cos + (long)pos * HD + g * 4 : nullptr,
+    store_grad_row<HD>(kp, dk, p.scale, p.rope_cos ? p.rope_cos + (long)pos * HD + g * 4 : nullptr,
                    p.rope_sin ? p.rope_sin + (long)pos * HD + g * 4 : nullptr);
-    store_grad_row(kp + p.H * HD, dv, 1.f, nullptr, nullptr);
+    store_grad_row<HD>(kp + p.H * HD, dv, 1.f, nullptr, nullptr);
 }
 
 // grid (B*H, T * nSB): 64 queries of one step per block (wave w: 16 of them); key tiles of 64: the sample's prefix, then the step's own rows
+template <int HD>
 __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     LDS_PTR(char) smem = (LDS_PTR(char))smem_raw;
-    constexpr int TILE = 64 * ROWB;
+    constexpr int TILE = 64 * HD * 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
     const int T = p.T, ld = p.ld, od = p.H * HD;
@@ -1123,20 +1163,20 @@ __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
     const int lp = p.cu[b + 1] - p.cu[b];
     const int qi = lane & 15, g = lane >> 4;
     const int q = q0 + wave * 16 + qi;
-    f32x4 dq[8];
+    f32x4 dq[HD / 16];
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < HD / 16; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     if (q0 < n) {
         const u32x4 rpre = make_desc_u(p.qkv + (long)p.cu[b] * ld, (uint32_t)(((long)(lp - 1) * ld + 3 * p.H * HD) * 2));
         const u32x4 rstep = make_desc_u(p.qkv + row0 * ld, (uint32_t)(((long)(n - 1) * ld + 3 * p.H * HD) * 2));
         const int kcol = p.H * HD + h * HD, vcol = 2 * p.H * HD + h * HD;
         const int ql = q < n ? q : n - 1;
-        bf16x8 qf[4], dof[4];
+        bf16x8 qf[HD / 32], dof[HD / 32];
         {
             const bf16_t* qp = p.qkv + (row0 + ql) * ld + h * HD + g * 8;
             const bf16_t* dp_ = p.dout + (row0 + ql) * od + h * HD + g * 8;
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
+            for (int kk = 0; kk < HD / 32; ++kk) {
                 qf[kk] = *(const bf16x8*)(qp + kk * 32);
                 dof[kk] = *(const bf16x8*)(dp_ + kk * 32);
             }
@@ -1147,16 +1187,16 @@ __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
         const int npt = (lp + 63) / 64, total = npt + q_hi / 64 + 1;
         auto stage = [&](int i, int buf) {
             if (i < npt) {
-                stage_rows<64, 256>(rpre, smem + buf * 2 * TILE, i * 64, kcol, ld, tid);
-                stage_rows<64, 256>(rpre, smem + buf * 2 * TILE + TILE, i * 64, vcol, ld, tid);
+                stage_rows<HD, 64, 256>(rpre, smem + buf * 2 * TILE, i * 64, kcol, ld, tid);
+                stage_rows<HD, 64, 256>(rpre, smem + buf * 2 * TILE + TILE, i * 64, vcol, ld, tid);
             } else {
-                stage_rows<64, 256>(rstep, smem + buf * 2 * TILE, (i - npt) * 64, kcol, ld, tid);
-                stage_rows<64, 256>(rstep, smem + buf * 2 * TILE + TILE, (i - npt) * 64, vcol, ld, tid);
+                stage_rows<HD, 64, 256>(rstep, smem + buf * 2 * TILE, (i - npt) * 64, kcol, ld, tid);
+                stage_rows<HD, 64, 256>(rstep, smem + buf * 2 * TILE + TILE, (i - npt) * 64, vcol, ld, tid);
             }
         };
         stage(0, 0);
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) { pin(qf[kk]); pin(dof[kk]); }
+        for (int kk = 0; kk < HD / 32; ++kk) { pin(qf[kk]); pin(dof[kk]); }
         float lse_q = my_lse, ds_q = my_ds;
         pin(lse_q); pin(ds_q);
         wait_vmcnt<0>();
@@ -1169,7 +1209,7 @@ __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
             const bool is_pre = i < npt;
             const int kt = is_pre ? i : i - npt;
             const bool interior = (wq_hi < n) && (is_pre ? kt * 64 + 63 < lp : kt * 64 + 63 <= wq_lo);
-            dq_tile(dq, sk, sk + TILE, qf, dof, lse_q, ds_q, kt * 64, interior, [&](int key) { return q < n && (is_pre ? key < lp : key <= q); },
+            dq_tile<HD>(dq, sk, sk + TILE, qf, dof, lse_q, ds_q, kt * 64, interior, [&](int key) { return q < n && (is_pre ? key < lp : key <= q); },
                     p.scale2, lane);
             wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
@@ -1179,12 +1219,86 @@ __global__ __launch_bounds__(256) void epi_bwd_dq_kernel(EpiArgs p) {
     if (q >= n) return;
     const int pos = lp + q < p.cap ? lp + q : p.cap - 1;
     bf16_t* qp = p.dqkv + (row0 + q) * ld + h * HD + g * 4;
-    store_grad_row(qp, dq, p.scale, p.rope_cos ? p.rope_cos + (long)pos * HD + g * 4 : nullptr,
+    store_grad_row<HD>(qp, dq, p.scale, p.rope_cos ? p.rope_cos + (long)pos * HD + g * 4 : nullptr,
                    p.rope_sin ? p.rope_sin + (long)pos * HD + g * 4 : nullptr);
 }
 
 int set_lds(const void* fn, int bytes) {
     return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? NV_OK : NV_ERR_LAUNCH;
+}
+
+// ---- host side: the entry points check their arguments, fill the width-independent argument block and hand it to the
+// instantiation of their head_dim (hd_ok has been checked by then)
+bool hd_ok(int head_dim) { return head_dim == 64 || head_dim == 128; }
+#define NV_FOR_HD(head_dim, fn, ...) ((head_dim) == 64 ? fn<64>(__VA_ARGS__) : fn<128>(__VA_ARGS__))
+
+void set_scales(AttnArgs& p, int head_dim) {
+    p.scale = 1.f / sqrtf((float)head_dim); p.scale2 = p.scale * 1.4426950408889634f;
+}
+
+// forward: two (K, V) tile pairs of 64 rows = 64 KiB at head_dim 128, 32 KiB at 64
+template <int HD>
+int launch_fwd(const AttnArgs& p, int qblocks, hipStream_t st) {
+    constexpr int LDS = 4 * 64 * HD * 2;
+    static bool once = false;
+    if (!once) { if (set_lds((const void*)attn_fwd_kernel<HD, false>, LDS)) return NV_ERR_LAUNCH; once = true; }
+    NV_LAUNCH((attn_fwd_kernel<HD, false>), dim3(p.B * p.H, qblocks), dim3(256), LDS, st, p);
+    return nv_check_launch();
+}
+
+template <int HD>
+int launch_epi_fwd(const EpiFwdArgs& p, hipStream_t st) {
+    constexpr int LDS = 4 * 64 * HD * 2;
+    static bool once = false;
+    if (!once) { if (set_lds((const void*)epi_fwd_kernel<HD>, LDS)) return NV_ERR_LAUNCH; once = true; }
+    NV_LAUNCH(epi_fwd_kernel<HD>, dim3(p.B * p.H, p.T * p.QB), dim3(256), LDS, st, p);
+    return nv_check_launch();
+}
+
+template <int HD>
+int launch_decode(const bf16_t* kv, const int* crow, const int* pos, bf16_t* out, int M, int H, int cap, hipStream_t st) {
+    const float scale2 = (1.f / sqrtf((float)HD)) * 1.4426950408889634f;
+    NV_LAUNCH(attn_decode_kernel<HD>, dim3(H, M), dim3(DEC_WAVES * 64), 0, st, kv, crow, pos, out, H, cap, scale2);
+    return nv_check_launch();
+}
+
+// backward: dsum, then dK/dV (4 slots x (Q, dO) tiles of 32 rows, then the statistics: two blocks per CU) and dQ (as the forward)
+template <int HD>
+int launch_bwd(AttnArgs p, const bf16_t* out, long rows, int q_lo, int nq, int dq_blocks, hipStream_t st) {
+    constexpr int RING = DKV_SLOTS * 2 * 32 * HD * 2, DQ_LDS = 4 * 64 * HD * 2;
+    static bool once = false;
+    if (!once) {
+        if (set_lds((const void*)attn_bwd_dkv_kernel<HD>, RING + 12288) || set_lds((const void*)attn_bwd_dq_kernel<HD>, DQ_LDS)) return NV_ERR_LAUNCH;
+        once = true;
+    }
+    constexpr int IPB = 256 / (HD / 8);                       // (row, head) items per block of the prep kernel
+    const long items = rows * p.H;
+    NV_LAUNCH(attn_bwd_prep_kernel<HD>, dim3((unsigned)((items + IPB - 1) / IPB)), dim3(256), 0, st, p.dout, out, (float*)p.dsum, p.cu, rows,
+              p.B, p.cu ? p.S : p.Sst, p.H, q_lo, nq);
+    const int dkv_lds = RING + 8 * p.stat_cap;
+    // with q_row_min > 0 only those query rows carry gradient: dK/dV still cover every key, dQ rows below
+    // q_row_min are NOT written (the caller zero-fills them)
+    NV_LAUNCH(attn_bwd_dkv_kernel<HD>, dim3(p.B * p.H, (p.S + 63) / 64), dim3(256), dkv_lds, st, p);
+    NV_LAUNCH(attn_bwd_dq_kernel<HD>, dim3(p.B * p.H, dq_blocks), dim3(256), DQ_LDS, st, p);
+    return nv_check_launch();
+}
+
+template <int HD>
+int launch_epi_bwd(const EpiArgs& p, const bf16_t* out, int Mp, hipStream_t st) {
+    constexpr int RING = DKV_SLOTS * 2 * 32 * HD * 2, DQ_LDS = 4 * 64 * HD * 2;
+    static bool once = false;
+    if (!once) {
+        if (set_lds((const void*)epi_bwd_dkv_kernel<HD>, RING + 12288) || set_lds((const void*)epi_bwd_dq_kernel<HD>, DQ_LDS)) return NV_ERR_LAUNCH;
+        once = true;
+    }
+    constexpr int IPB = 256 / (HD / 8);
+    const int od = p.H * HD;
+    const long Rs = p.Rs;
+    NV_LAUNCH(attn_bwd_prep_kernel<HD>, dim3((unsigned)((Rs * p.H + IPB - 1) / IPB)), dim3(256), 0, st, p.dout + (long)Mp * od,
+              out + (long)Mp * od, (float*)p.dsum, (const int*)nullptr, Rs, 1, (int)Rs, p.H, 0, (int)Rs);
+    NV_LAUNCH(epi_bwd_dkv_kernel<HD>, dim3(p.B * p.H, p.nPB + p.T * p.nSB), dim3(256), RING + 8 * p.stat_cap, st, p);
+    NV_LAUNCH(epi_bwd_dq_kernel<HD>, dim3(p.B * p.H, p.T * p.nSB), dim3(256), DQ_LDS, st, p);
+    return nv_check_launch();
 }
 
 }  // namespace
@@ -1194,16 +1308,13 @@ extern "C" {
 int nv_attn_fwd_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, int B, int S, int H, int head_dim,
                      int q_row_min, void* stream) {
     if (!qkv || !out || !lse2 || !kv_start) return NV_ERR_ARG;
-    if (head_dim != HD || (q_row_min & 127) || q_row_min < 0 || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || (q_row_min & 127) || q_row_min < 0 || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
     if (B == 0 || S == 0) return NV_OK;
-    static bool once = false;
-    if (!once) { if (set_lds((const void*)attn_fwd_kernel<false>, 65536)) return NV_ERR_LAUNCH; once = true; }
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse2 = lse2; p.kv_start = kv_start;
-    p.B = B; p.S = S; p.Sst = S; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
-    NV_LAUNCH(attn_fwd_kernel<false>, dim3(B * H, (S - q_row_min + 127) / 128), dim3(256), 65536, (hipStream_t)stream, p);
-    return nv_check_launch();
+    p.B = B; p.S = S; p.Sst = S; p.H = H; p.ld = 3 * H * head_dim; p.q_row_min = q_row_min;
+    set_scales(p, head_dim);
+    return NV_FOR_HD(head_dim, launch_fwd, p, (S - q_row_min + 127) / 128, (hipStream_t)stream);
 }
 
 // The same forward over a KV-cache layout: sample b's rows start at b*S_stride (S_stride >= S = the longest valid
@@ -1211,52 +1322,43 @@ int nv_attn_fwd_bf16(const void* qkv, void* out, float* lse2, const int* kv_star
 int nv_attn_fwd_strided_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, int B, int S, int S_stride, int H,
                              int head_dim, int q_row_min, void* stream) {
     if (!qkv || !out || !lse2 || !kv_start) return NV_ERR_ARG;
-    if (head_dim != HD || (q_row_min & 127) || q_row_min < 0 || (S > 0 && q_row_min >= S) || S_stride < S) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || (q_row_min & 127) || q_row_min < 0 || (S > 0 && q_row_min >= S) || S_stride < S) return NV_ERR_SHAPE;
     if (B == 0 || S == 0) return NV_OK;
-    static bool once = false;
-    if (!once) { if (set_lds((const void*)attn_fwd_kernel<false>, 65536)) return NV_ERR_LAUNCH; once = true; }
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse2 = lse2; p.kv_start = kv_start;
-    p.B = B; p.S = S; p.Sst = S_stride; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
-    NV_LAUNCH(attn_fwd_kernel<false>, dim3(B * H, (S - q_row_min + 127) / 128), dim3(256), 65536, (hipStream_t)stream, p);
-    return nv_check_launch();
+    p.B = B; p.S = S; p.Sst = S_stride; p.H = H; p.ld = 3 * H * head_dim; p.q_row_min = q_row_min;
+    set_scales(p, head_dim);
+    return NV_FOR_HD(head_dim, launch_fwd, p, (S - q_row_min + 127) / 128, (hipStream_t)stream);
 }
 
 // Forward attention of ALL steps of a prefix-reuse episode in one launch, reading the episode row buffers in place (see
-// epi_fwd_kernel): qkv [rows, 3*H*128] post-RoPE (prefix rows of sample b at [cu[b], cu[b+1]), step t's rows of sample b at
-// [tab[t*B+b], + tab[T*B + t*B + b])), out [rows, H*128] written at the steps' rows, lse_ptrs[t] -> fp32 [B, H, cap] of step t written
+// epi_fwd_kernel): qkv [rows, 3*H*head_dim] post-RoPE (prefix rows of sample b at [cu[b], cu[b+1]), step t's rows of sample b at
+// [tab[t*B+b], + tab[T*B + t*B + b])), out [rows, H*head_dim] written at the steps' rows, lse_ptrs[t] -> fp32 [B, H, cap] of step t written
 // at cache position prefix_len + j.  n_max = the longest per-sample row count of a step.  Bit-identical to scattering each step
 // into the K/V-cache layout + nv_attn_fwd_strided_bf16 + gathering back.
 int nv_attn_fwd_episode_bf16(const void* qkv, void* out, const void* lse_ptrs, const int* cu, const int* tab, int T, int B, int H,
                              int head_dim, int cap, int n_max, long rows, void* stream) {
     if (!qkv || !out || !lse_ptrs || !cu || !tab || T < 0 || B <= 0 || H <= 0 || cap <= 0 || rows <= 0) return NV_ERR_ARG;
-    if (head_dim != HD) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim)) return NV_ERR_SHAPE;
     if (T == 0 || n_max <= 0) return NV_OK;
-    const long bytes = rows * 3L * H * HD * 2;
+    const long bytes = rows * 3L * H * head_dim * 2;
     if (bytes > 0xffffffffL) return NV_ERR_SHAPE;
     if ((long)T * ((n_max + 127) / 128) > 65535) return NV_ERR_SHAPE;      // grid.y limit: the caller takes the per-step path
-    static bool once = false;
-    if (!once) { if (set_lds((const void*)epi_fwd_kernel, 65536)) return NV_ERR_LAUNCH; once = true; }
     EpiFwdArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse = (float* const*)lse_ptrs; p.cu = cu; p.tab = tab;
-    p.T = T; p.B = B; p.H = H; p.ld = 3 * H * HD; p.cap = cap; p.QB = (n_max + 127) / 128;
+    p.T = T; p.B = B; p.H = H; p.ld = 3 * H * head_dim; p.cap = cap; p.QB = (n_max + 127) / 128;
     p.span = (uint32_t)bytes;
-    p.scale2 = (1.f / sqrtf((float)HD)) * 1.4426950408889634f;
-    NV_LAUNCH(epi_fwd_kernel, dim3(B * H, T * p.QB), dim3(256), 65536, (hipStream_t)stream, p);
-    return nv_check_launch();
+    p.scale2 = (1.f / sqrtf((float)head_dim)) * 1.4426950408889634f;
+    return NV_FOR_HD(head_dim, launch_epi_fwd, p, (hipStream_t)stream);
 }
 
 // Decode attention: query r = the q slice of cache row crow[r] of SAMPLE r (one new token per sample), keys/values = cache rows
-// r*cap + [0, pos[r]], out [M, H*128] compact.  pos / crow are device arrays: nothing in the launch depends on the lengths.
+// r*cap + [0, pos[r]], out [M, H*head_dim] compact.  pos / crow are device arrays: nothing in the launch depends on the lengths.
 int nv_attn_decode_bf16(const void* kv, const int* crow, const int* pos, void* out, int M, int H, int head_dim, int cap, void* stream) {
     if (!kv || !crow || !pos || !out || cap <= 0) return NV_ERR_ARG;
-    if (head_dim != HD) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim)) return NV_ERR_SHAPE;
     if (M == 0) return NV_OK;
-    const float scale2 = (1.f / sqrtf((float)HD)) * 1.4426950408889634f;
-    NV_LAUNCH(attn_decode_kernel, dim3(H, M), dim3(DEC_WAVES * 64), 0, (hipStream_t)stream, (const bf16_t*)kv, crow, pos, (bf16_t*)out, H, cap,
-              scale2);
-    return nv_check_launch();
+    return NV_FOR_HD(head_dim, launch_decode, (const bf16_t*)kv, crow, pos, (bf16_t*)out, M, H, cap, (hipStream_t)stream);
 }
 
 // The same over a K/V cache whose current length and first computed query row live in DEVICE memory: dyn = {S, q_row_min}
@@ -1264,16 +1366,13 @@ int nv_attn_decode_bf16(const void* kv, const int* crow, const int* pos, void* o
 int nv_attn_fwd_strided_dyn_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, int B, int S_stride, int H, int head_dim,
                                  const int* dyn, void* stream) {
     if (!qkv || !out || !lse2 || !kv_start || !dyn) return NV_ERR_ARG;
-    if (head_dim != HD || S_stride <= 0) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || S_stride <= 0) return NV_ERR_SHAPE;
     if (B == 0) return NV_OK;
-    static bool once = false;
-    if (!once) { if (set_lds((const void*)attn_fwd_kernel<false>, 65536)) return NV_ERR_LAUNCH; once = true; }
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse2 = lse2; p.kv_start = kv_start;
-    p.B = B; p.S = S_stride; p.Sst = S_stride; p.H = H; p.ld = 3 * H * HD; p.q_row_min = 0; p.dyn = dyn;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
-    NV_LAUNCH(attn_fwd_kernel<false>, dim3(B * H, (S_stride + 127) / 128), dim3(256), 65536, (hipStream_t)stream, p);
-    return nv_check_launch();
+    p.B = B; p.S = S_stride; p.Sst = S_stride; p.H = H; p.ld = 3 * H * head_dim; p.q_row_min = 0; p.dyn = dyn;
+    set_scales(p, head_dim);
+    return NV_FOR_HD(head_dim, launch_fwd, p, (S_stride + 127) / 128, (hipStream_t)stream);
 }
 
 // Packed ("varlen") rows: sample b = rows [cu[b], cu[b+1]) of qkv / out (cu: int32 [B+1] on the device), S_max = the
@@ -1283,35 +1382,34 @@ int nv_attn_fwd_strided_dyn_bf16(const void* qkv, void* out, float* lse2, const 
 int nv_attn_fwd_varlen_bf16(const void* qkv, void* out, float* lse2, const int* cu, const int* pos0, int B, int S_max, int H,
                             int head_dim, int q_row_min, void* stream) {
     if (!qkv || !out || !lse2 || !cu || !pos0) return NV_ERR_ARG;
-    if (head_dim != HD || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < -1 || (S_max > 0 && q_row_min >= S_max)) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < -1 || (S_max > 0 && q_row_min >= S_max)) return NV_ERR_SHAPE;
     if (B == 0 || S_max == 0) return NV_OK;
-    static bool once = false;
-    if (!once) { if (set_lds((const void*)attn_fwd_kernel<false>, 65536)) return NV_ERR_LAUNCH; once = true; }
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse2 = lse2; p.kv_start = pos0; p.cu = cu;
-    p.B = B; p.S = S_max; p.Sst = S_max; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
+    p.B = B; p.S = S_max; p.Sst = S_max; p.H = H; p.ld = 3 * H * head_dim; p.q_row_min = q_row_min;
+    set_scales(p, head_dim);
     const int qblocks = q_row_min < 0 ? 1 : (S_max - q_row_min + 127) / 128;
-    NV_LAUNCH(attn_fwd_kernel<false>, dim3(B * H, qblocks), dim3(256), 65536, (hipStream_t)stream, p);
-    return nv_check_launch();
+    return NV_FOR_HD(head_dim, launch_fwd, p, qblocks, (hipStream_t)stream);
 }
 
 // PARITY INSTRUMENT (tests only; never called by navillm_amd's forward): the same attention with HF's eager-attention rounding
-// points (attn_fwd_kernel<true>, two passes).  cu == NULL: padded [B, S] layout with kv_start; else packed rows (kv_start =
-// pos0).  Same outputs / layouts as nv_attn_fwd_bf16 resp. nv_attn_fwd_varlen_bf16.
+// points (attn_fwd_kernel<128, true>, two passes).  head_dim 128 only: the reference models it is compared with are 128 wide.
+// cu == NULL: padded [B, S] layout with kv_start; else packed rows (kv_start = pos0).  Same outputs / layouts as nv_attn_fwd_bf16
+// resp. nv_attn_fwd_varlen_bf16.
 int nv_attn_fwd_hfround_bf16(const void* qkv, void* out, float* lse2, const int* kv_start, const int* cu, int B, int S, int H,
                              int head_dim, int q_row_min, void* stream) {
+    constexpr int HD = 128;
     if (!qkv || !out || !lse2 || !kv_start) return NV_ERR_ARG;
     if (head_dim != HD || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < (cu ? -1 : 0) || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
     if (B == 0 || S == 0) return NV_OK;
     static bool once = false;
-    if (!once) { if (set_lds((const void*)attn_fwd_kernel<true>, 65536)) return NV_ERR_LAUNCH; once = true; }
+    if (!once) { if (set_lds((const void*)attn_fwd_kernel<HD, true>, 65536)) return NV_ERR_LAUNCH; once = true; }
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.out = (bf16_t*)out; p.lse2 = lse2; p.kv_start = kv_start; p.cu = cu;
     p.B = B; p.S = S; p.Sst = S; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
+    set_scales(p, HD);
     const int qblocks = q_row_min < 0 ? 1 : (S - q_row_min + 127) / 128;
-    NV_LAUNCH(attn_fwd_kernel<true>, dim3(B * H, qblocks), dim3(256), 65536, (hipStream_t)stream, p);
+    NV_LAUNCH((attn_fwd_kernel<HD, true>), dim3(B * H, qblocks), dim3(256), 65536, (hipStream_t)stream, p);
     return nv_check_launch();
 }
 
@@ -1323,38 +1421,25 @@ static int attn_bwd_impl(const void* qkv, const void* out, const void* dout, con
                          const void* rope_sin, void* stream, const int* cu = nullptr, long rows = -1, int Sst = 0, float* kvacc = nullptr,
                          const int* kvacc_len = nullptr, int kvacc_add = 0) {
     if (!qkv || !out || !dout || !lse2 || !kv_start || !dqkv || !workspace) return NV_ERR_ARG;
-    if (head_dim != HD || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < (cu ? -1 : 0) || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || (q_row_min >= 0 && (q_row_min & 127)) || q_row_min < (cu ? -1 : 0) || (S > 0 && q_row_min >= S)) return NV_ERR_SHAPE;
     if ((rope_cos == nullptr) != (rope_sin == nullptr)) return NV_ERR_ARG;
     if (B == 0 || S == 0) return NV_OK;
-    static bool once = false;
-    if (!once) {
-        if (set_lds((const void*)attn_bwd_dkv_kernel, 77824) || set_lds((const void*)attn_bwd_dq_kernel, 65536)) return NV_ERR_LAUNCH;
-        once = true;
-    }
-    hipStream_t st = (hipStream_t)stream;
     float* dsum = (float*)workspace;
     if (Sst <= 0) Sst = S;
     // padded / strided (K/V-cache) layout: dsum is indexed like lse2, [B, H, Sst]; only the query rows [q_row_min, S) of a sample are
     // read by the kernels below
     const int q_lo = cu ? 0 : q_row_min, nq = cu ? 0 : S - q_row_min;
     if (rows < 0) rows = (long)B * nq;
-    const long items = rows * H;
-    NV_LAUNCH(attn_bwd_prep_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, st, (const bf16_t*)dout,
-                       (const bf16_t*)out, dsum, cu, rows, B, cu ? S : Sst, H, q_lo, nq);
     AttnArgs p{};
     p.qkv = (const bf16_t*)qkv; p.dout = (const bf16_t*)dout; p.lse2 = (float*)lse2; p.dsum = dsum; p.dqkv = (bf16_t*)dqkv;
-    p.kv_start = kv_start; p.cu = cu; p.B = B; p.S = S; p.Sst = Sst; p.H = H; p.ld = 3 * H * HD; p.q_row_min = q_row_min;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
+    p.kv_start = kv_start; p.cu = cu; p.B = B; p.S = S; p.Sst = Sst; p.H = H; p.ld = 3 * H * head_dim; p.q_row_min = q_row_min;
+    set_scales(p, head_dim);
     p.rope_cos = (const bf16_t*)rope_cos; p.rope_sin = (const bf16_t*)rope_sin;
     p.kvacc = kvacc; p.kvacc_len = kvacc_len; p.kvacc_add = kvacc_add;
     const int scap = (S + 31) & ~31;
     p.stat_cap = 8 * scap <= 12288 ? scap : 0;                // dK/dV: lse + dsum of one (sample, head) in LDS when they fit (S <= 1536)
-    const int dkv_lds = 65536 + 8 * p.stat_cap;               // 4 slots x (Q, dO) x 8 KiB, then the statistics: two blocks per CU
-    // with q_row_min > 0 only those query rows carry gradient: dK/dV still cover every key, dQ rows below
-    // q_row_min are NOT written (the caller zero-fills them)
-    NV_LAUNCH(attn_bwd_dkv_kernel, dim3(B * H, (S + 63) / 64), dim3(256), dkv_lds, st, p);
-    NV_LAUNCH(attn_bwd_dq_kernel, dim3(B * H, q_row_min < 0 ? 2 : (S - q_row_min + 63) / 64), dim3(256), 65536, st, p);
-    return nv_check_launch();
+    const int dq_blocks = q_row_min < 0 ? 2 : (S - q_row_min + 63) / 64;
+    return NV_FOR_HD(head_dim, launch_bwd, p, (const bf16_t*)out, rows, q_lo, nq, dq_blocks, (hipStream_t)stream);
 }
 
 int nv_attn_bwd_bf16(const void* qkv, const void* out, const void* dout, const float* lse2, const int* kv_start, void* dqkv,
@@ -1362,7 +1447,7 @@ int nv_attn_bwd_bf16(const void* qkv, const void* out, const void* dout, const f
     return attn_bwd_impl(qkv, out, dout, lse2, kv_start, dqkv, workspace, B, S, H, head_dim, q_row_min, nullptr, nullptr, stream);
 }
 
-// The same with the transpose of RoPE applied to dQ and dK as they are written (cos/sin: the [maxS, 128] bf16 tables of
+// The same with the transpose of RoPE applied to dQ and dK as they are written (cos/sin: the [maxS, head_dim] bf16 tables of
 // nv_rope_bf16; position of a row = its index within the sample): saves the separate in-place pass over dqkv.
 int nv_attn_bwd_rope_bf16(const void* qkv, const void* out, const void* dout, const float* lse2, const int* kv_start, void* dqkv,
                           void* workspace, const void* rope_cos, const void* rope_sin, int B, int S, int H, int head_dim,
@@ -1425,31 +1510,19 @@ int nv_attn_bwd_episode_acc_bf16(const void* qkv, const void* out, const void* d
                                  int head_dim, int cap, int Mp, long R, int Lp_max, int N_max, int accumulate, void* stream) {
     if (!qkv || !out || !dout || !dqkv || !workspace || !lse_ptrs || !cu || !tab || !kv_acc) return NV_ERR_ARG;
     if ((rope_cos == nullptr) != (rope_sin == nullptr)) return NV_ERR_ARG;
-    if (head_dim != HD || T < 0 || B <= 0 || H <= 0 || cap <= 0 || Mp < 0 || R < Mp || Lp_max <= 0 || Lp_max > cap || N_max < 0) return NV_ERR_SHAPE;
+    if (!hd_ok(head_dim) || T < 0 || B <= 0 || H <= 0 || cap <= 0 || Mp < 0 || R < Mp || Lp_max <= 0 || Lp_max > cap || N_max < 0) return NV_ERR_SHAPE;
     if (T == 0 || R == Mp || N_max == 0) return NV_OK;
     const int scap = (N_max + 31) & ~31;
     if (T > EPI_TMAX || 8 * scap > 12288) return NV_ERR_SHAPE;    // step table / statistics rows beyond the LDS budget (N_max <= 1536)
-    static bool once = false;
-    if (!once) {
-        if (set_lds((const void*)epi_bwd_dkv_kernel, 77824) || set_lds((const void*)epi_bwd_dq_kernel, 65536)) return NV_ERR_LAUNCH;
-        once = true;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const int od = H * HD;
     const long Rs = R - Mp;
-    float* dsum = (float*)workspace;
-    NV_LAUNCH(attn_bwd_prep_kernel, dim3((unsigned)((Rs * H + 15) / 16)), dim3(256), 0, st, (const bf16_t*)dout + (long)Mp * od,
-              (const bf16_t*)out + (long)Mp * od, dsum, (const int*)nullptr, Rs, 1, (int)Rs, H, 0, (int)Rs);
     EpiArgs p{};
-    p.qkv = (const bf16_t*)qkv; p.dout = (const bf16_t*)dout; p.dqkv = (bf16_t*)dqkv; p.dsum = dsum;
+    p.qkv = (const bf16_t*)qkv; p.dout = (const bf16_t*)dout; p.dqkv = (bf16_t*)dqkv; p.dsum = (const float*)workspace;
     p.lse = (const float* const*)lse_ptrs; p.cu = cu; p.tab = tab; p.kvacc = kv_acc;
     p.rope_cos = (const bf16_t*)rope_cos; p.rope_sin = (const bf16_t*)rope_sin;
-    p.T = T; p.B = B; p.H = H; p.ld = 3 * H * HD; p.cap = cap; p.Mp = Mp; p.Rs = (int)Rs;
+    p.T = T; p.B = B; p.H = H; p.ld = 3 * H * head_dim; p.cap = cap; p.Mp = Mp; p.Rs = (int)Rs;
     p.nPB = (Lp_max + 63) / 64; p.nSB = (N_max + 63) / 64; p.stat_cap = scap; p.kvacc_add = accumulate ? 1 : 0;
-    p.scale = 1.f / sqrtf((float)HD); p.scale2 = p.scale * 1.4426950408889634f;
-    NV_LAUNCH(epi_bwd_dkv_kernel, dim3(B * H, p.nPB + T * p.nSB), dim3(256), 65536 + 8 * scap, st, p);
-    NV_LAUNCH(epi_bwd_dq_kernel, dim3(B * H, T * p.nSB), dim3(256), 65536, st, p);
-    return nv_check_launch();
+    p.scale = 1.f / sqrtf((float)head_dim); p.scale2 = p.scale * 1.4426950408889634f;
+    return NV_FOR_HD(head_dim, launch_epi_bwd, p, (const bf16_t*)out, Mp, (hipStream_t)stream);
 }
 
 

@@ -52,7 +52,7 @@ struct nv_decoder {
 extern "C" {
 
 nv_decoder* nv_decoder_create(int L, int d, int H, int head_dim, int ff, float eps) {
-    if (L <= 0 || d <= 0 || H <= 0 || head_dim != 128 || H * head_dim != d || ff <= 0) return nullptr;
+    if (L <= 0 || d <= 0 || H <= 0 || (head_dim != 64 && head_dim != 128) || H * head_dim != d || ff <= 0) return nullptr;   // the attention widths
     nv_decoder* p = new (std::nothrow) nv_decoder();
     if (!p) return nullptr;
     p->L = L; p->d = d; p->H = H; p->hd = head_dim; p->ff = ff; p->eps = eps;
@@ -218,6 +218,8 @@ int nv_decoder_extend(const nv_decoder* p, const void* x_in, const int* pos, con
     const char* knob2 = getenv("NV_DECODE_ATTN");
     // one new row per sample (M == B: row r is sample r): the streaming decode attention, output rows compact in `attn`
     const bool dec_attn = !(knob2 && atoi(knob2) == 0) && M == B;
+    // (the width conditions are the weight streamer's, K % 128 with fp8 codes; they do not involve the head width: a 768 x 3072 model
+    // with 64-wide heads takes the fused route, whose RoPE + scatter and attention launches get p->hd like the unfused ones)
     const bool fused = !(knob && atoi(knob) == 0) && M <= 16 && (d % 128) == 0 && (ff % 128) == 0;
     // weight-only fp8 with the de-quantisation overlapped (see nv_decoder_set_fp8_overlap): every layer must carry codes only
     Fp8Pipe pipe{p, (hipStream_t)stream, false, {{3 * (int)d, (int)d}, {(int)d, (int)d}, {2 * (int)ff, (int)d}, {(int)d, (int)ff}}};

@@ -538,7 +538,7 @@ class PrefixEpisode:
                     return self._E[i + 1]["x"][:Mp]        # a layer's output IS the next layer's saved input
                 return self._buf(f"p{i}.{name}", (Mp, width) if width else (Mp,), dt)
             n1, rstd1 = ops.rmsnorm_fwd(x, w1, eps, out=t("n1", d), rstd=t("r1", 0, F32))
-            qkv = ops.gemm_qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, Lmax, 2 * H * hd, out=t("qkv", 3 * d), pos_i32=pos_d)
+            qkv = ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, Lmax, H, hd, out=t("qkv", 3 * d), pos_i32=pos_d)
             if to_cache:
                 ops.scatter_rows_bf16_(qkv, crow_d, self.cache[i])
             if i == L - 1 and os.environ.get("NAVILLM_EPISODE_PRUNE_TOP", "1") != "0":
@@ -767,7 +767,7 @@ class PrefixEpisode:
                 return self._buf(f"s{i}.{name}", (M, width) if width else (M,), dt)
             n1, rstd1 = ops.rmsnorm_fwd(x, w1, eps, out=t("n1", d), rstd=t("r1", 0, F32))
             # q|k|v with RoPE in the GEMM epilogue (bit-identical to the GEMM followed by nv_rope_rows_bf16), row r at position pos[r]
-            qkv = ops.gemm_qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, 2 * H * hd, out=E["qkv"][r0:r0 + M] if allm else self._buf("qkv", (M, 3 * d)),
+            qkv = ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][r0:r0 + M] if allm else self._buf("qkv", (M, 3 * d)),
                                     pos_i32=step["pos"])
             attn = t("attn", d)
             if epi:
@@ -1031,7 +1031,7 @@ class PrefixEpisode:
                 Wqkv, Wo, Wgu, Wd, w1, w2 = self._weights(i)[:6]
                 E, E32 = self._E[i], self._E32[i]
                 n1, _ = ops.rmsnorm_fwd(x, w1, eps, out=E["n1"][rows], rstd=E32["r1"][rows])
-                ops.gemm_qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, 2 * H * hd, out=E["qkv"][rows], pos_i32=pos_cat)
+                ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][rows], pos_i32=pos_cat)
                 if pend:
                     # the prefix rows' own causal attention (the top layer's is never read: only its K/V are, by the steps' queries)
                     if i < L - 1 or not prune_top:

@@ -407,7 +407,7 @@ class LlamaStack(torch.autograd.Function):
 
         def qkv_proj(n1, i, a):
             if FUSE_ROPE_FWD and M > 16:
-                return ops.gemm_qkv_rope(n1, model.lm_w(i, "qkv"), model.rope_cos, model.rope_sin, S, 2 * H * hd, out=a["qkv"][:M], pos_i32=pos)
+                return ops.qkv_rope(n1, model.lm_w(i, "qkv"), model.rope_cos, model.rope_sin, S, H, hd, out=a["qkv"][:M], pos_i32=pos)
             qkv = model.lm_linear(n1, i, "qkv", out=a["qkv"][:M])
             if pos is not None:
                 return ops.rope_rows_(qkv, model.rope_cos, model.rope_sin, pos, H, hd)

@@ -95,8 +95,8 @@ class NavModel(nn.Module):
         if not cfg.lm_is_bf16:
             raise NotImplementedError("the MI355X path implements the reference's amp_bf16 mode (bf16 LM + heads, fp32 "
                                       "encoder); precision='fp32' has no HIP LM")
-        if cfg.head_dim != 128:
-            raise NotImplementedError("attention kernels are built for head_dim 128 (Llama/Vicuna 7B/13B)")
+        if cfg.hidden_size % cfg.num_heads or cfg.head_dim not in (64, 128):
+            raise NotImplementedError(f"attention kernels are built for head_dim 64 and 128, not {cfg.hidden_size} / {cfg.num_heads}")
         if device is None:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
@@ -245,6 +245,8 @@ class NavModel(nn.Module):
         from .fp8 import Fp8DecoderWeights
         if self.fp8 is not None:
             return self.fp8
+        if self.cfg.head_dim != 128:
+            raise NotImplementedError("weight-only fp8 is built and tested for head_dim 128 models only")
         torch.cuda.synchronize(self.device)
         self.fp8 = Fp8DecoderWeights(self, resident_bf16=resident_bf16, gemm_mode=gemm_mode)
         if resident_bf16:

@@ -109,6 +109,28 @@ def gemm_qkv_rope(x, Wqkv, cos_t, sin_t, S, rope_cols, out=None, pos_i32=None):
     return out
 
 
+def qkv_rope(x, Wqkv, cos_t, sin_t, S, H, hd, out=None, pos_i32=None):
+    """packed post-RoPE q|k|v = x @ Wqkv^T, q and k rotated; row m sits at position pos_i32[m] (packed rows) or m % S.
+    head_dim 128: RoPE in the GEMM epilogue (gemm_qkv_rope: its 256-wide tile holds two whole 128-wide heads).  Any other width
+    (64): the route include/navillm_hip.h documents as bit-identical to it -- the plain NT tile GEMM, whatever M, followed by
+    nv_rope_rows_bf16 / nv_rope_bf16.  The 128-wide epilogue would rotate the wrong column pairs of a 64-wide head."""
+    if hd == 128:
+        return gemm_qkv_rope(x, Wqkv, cos_t, sin_t, S, 2 * H * hd, out=out, pos_i32=pos_i32)
+    _chk2d(x, BF16)
+    _chk2d(Wqkv, BF16)
+    M, K = x.shape
+    N = Wqkv.shape[0]
+    assert N == 3 * H * hd and Wqkv.shape[1] == K, (Wqkv.shape, x.shape, H, hd)
+    if out is None:
+        out = torch.empty((M, N), dtype=BF16, device=x.device)
+    rc = _L().nv_gemm_bf16_ws(NT, x.data_ptr(), Wqkv.data_ptr(), out.data_ptr(), 0, M, N, K, x.stride(0), Wqkv.stride(0), out.stride(0), 0,
+                              EPI_STORE, 0, _gemm_ws(x.device) if SPLITK_TAIL else 0, _st())
+    _lib.check(rc, "nv_gemm_bf16_ws")
+    if pos_i32 is not None:
+        return rope_rows_(out, cos_t, sin_t, pos_i32, H, hd)
+    return rope_(out, cos_t, sin_t, S, H, hd)
+
+
 SPLITK_TAIL = True
 GEMV_DECODE = True      # M <= 16 NT GEMMs go to nv_gemv_bf16
 _gemm_ws_cache = {}
