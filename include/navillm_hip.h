@@ -362,14 +362,28 @@ int nv_rope_scatter_rows_bf16(const void* qkv, const void* cos_t, const void* si
  *      nv_decode_pick_bf16: masked argmax of logits [B, ldl] (ids >= V and [special0, special0+nspecial) excluded, ties -> smallest
  *      id), finished rows emit `pad`, a row finishes on `eos`; out[cnt, b] = token.  nv_decode_advance: cache indices of the new
  *      token from len, dyn = {max len + 1, 128-aligned min len}, len += 1, cnt += 1.  nv_decoder_greedy_step: lm_head -> pick ->
- *      advance -> embedding gather -> nv_decoder_extend(dyn); identical launch arguments every step (hipGraph replay). */
+ *      advance -> embedding gather -> nv_decoder_extend(dyn); identical launch arguments every step (hipGraph replay).
+ *      Trie-constrained form (TrieLogitsProcessor, models/modified_lm.py:10-30): the trie travels flattened (kvcache.flatten_trie) as
+ *      trie_off [n_nodes + 1], trie_tok [E], trie_nxt [E] -- node n owns the edges [trie_off[n], trie_off[n+1]), edge e carries token
+ *      trie_tok[e] and leads to node trie_nxt[e]; node 0 is the root, a leaf is one edge eos -> itself -- plus node [B], each sample's
+ *      current node (a buffer of its own: zero it before the first step).  nv_decode_pick_trie_bf16: the pick rule and bookkeeping of
+ *      nv_decode_pick_bf16 over the children of node[b] only, then node[b] = trie_nxt[winning edge] (a finished row keeps its node).
+ *      Table entries that point outside the tables are skipped, never followed; a node without a pickable child emits `eos` (the row
+ *      finishes) and keeps its node.  nv_decoder_trie_step: nv_decoder_greedy_step with that pick. */
 int nv_decode_state_ints(int B);
 int nv_decode_pick_bf16(const void* logits, int ldl, int V, int special0, int nspecial, int* state, int* out, int max_steps, int B, int eos,
                         int pad, void* stream);
+int nv_decode_pick_trie_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                             const int* trie_nxt, int n_nodes, int* node, int* state, int* out, int max_steps, int B, int eos, int pad,
+                             void* stream);
 int nv_decode_advance(int* state, int B, int cap, void* stream);
 int nv_decoder_greedy_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B,
                            int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream);
+int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
+                         const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, void* logits, void* x,
+                         int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange over RCCL (C0-C3): replaces the DDP gradient all-reduce behind tools/optims.py:52-54
  *      (+ its initial parameter broadcast) and the task-id broadcast of tasks/loaders.py:176-179.

@@ -30,8 +30,40 @@ from . import ops
 from . import debug as _debug
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
-DEVICE_GREEDY = os.environ.get("NAVILLM_DEVICE_GREEDY", "1") != "0"      # greedy decoding with the loop on the device (no trie)
+DEVICE_GREEDY = os.environ.get("NAVILLM_DEVICE_GREEDY", "1") != "0"      # greedy decoding (free or trie-constrained) with the loop on the device
 USE_HIP_GRAPH = os.environ.get("NAVILLM_DECODE_GRAPH", "1") != "0"       # ... replayed from a captured hipGraph
+
+
+def flatten_trie(trie, eos, V, special_ids):
+    """A trie of the tools/trie.py protocol as three int32 arrays (what `decode_pick_trie_kernel` walks): node n owns the edges
+    [off[n], off[n+1]), edge e carries token tok[e] and leads to node nxt[e].  Node 0 is the root, a node's edges are sorted by token
+    id, and a leaf is the one edge `eos -> itself` -- which is what the protocol says about it (get_child_index = [eos],
+    get_next_node = the node).  Built through `.root`, `.get_child_index(node)` and `.get_next_node(node, w)` alone, nodes told
+    apart by identity; get_next_node only ever sees tokens get_child_index just returned, so a trie that inserts on a miss
+    (the reference's defaultdict) keeps exactly the nodes it had.
+    -> (off [N+1], tok [E], nxt [E], eligible); eligible is False when some node has no pickable child (every child >= V or a
+    special id): what the host loop answers there is torch.argmax over an all -inf row, and such a trie stays on the host loop."""
+    special = set(int(t) for t in special_ids)
+    nodes, index = [trie.root], {id(trie.root): 0}                      # `nodes` keeps every node alive: ids stay unique
+    off, tok, nxt = [0], [], []
+    eligible = True
+    n = 0
+    while n < len(nodes):
+        cur = nodes[n]
+        n += 1
+        kids = sorted(set(int(w) for w in trie.get_child_index(cur)))
+        for w in kids:
+            child = trie.get_next_node(cur, w)
+            j = index.get(id(child))
+            if j is None:
+                j = index[id(child)] = len(nodes)
+                nodes.append(child)
+            tok.append(w)
+            nxt.append(j)
+        off.append(len(tok))
+        if not any(0 <= w < V and w not in special for w in kids):
+            eligible = False
+    return np.asarray(off, np.int32), np.asarray(tok, np.int32), np.asarray(nxt, np.int32), eligible
 
 
 class KVCacheLM:
@@ -46,7 +78,9 @@ class KVCacheLM:
         self.lse = torch.empty((batch_size, cfg.num_heads, capacity), dtype=F32, device=dev)
         self.kv0 = torch.zeros((batch_size,), dtype=I32, device=dev)
         self._dec, self._dec_key, self._ws = None, None, None
-        self._greedy = None                                    # device-side decode loop: buffers + captured hipGraph
+        self._greedy = None                                    # device-side decode loop: buffers + captured hipGraphs
+        self._trie_host, self._trie_dev = None, None           # the flattened trie of the last constrained call, host and device
+        self.last_generate = None                              # {"loop": "device" | "host", "trie": bool} of the last generate()
         self._key_ids = {}                                     # reuse key (hashable) -> small int
         self.reset()
 
@@ -226,8 +260,12 @@ class KVCacheLM:
         seqs = [list(x) for x in ids_list]
         vix = None if vis_idx_list is None else [list(v) for v in vis_idx_list]
         keys = None if vis_all is None else [("gen", r) for r in range(vis_all.shape[0])]   # constant within one call
-        if trie is None and not do_sample and DEVICE_GREEDY and max_new_tokens > 0 and max(len(x) for x in seqs) + max_new_tokens <= self.cap:
-            return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id)
+        self.last_generate = {"loop": "host", "trie": trie is not None}
+        if not do_sample and DEVICE_GREEDY and max_new_tokens > 0 and max(len(x) for x in seqs) + max_new_tokens <= self.cap:
+            tables = None if trie is None else self._trie_tables(trie, eos_token_id)
+            if trie is None or tables is not None:                 # (an ineligible trie keeps the host loop)
+                self.last_generate["loop"] = "device"
+                return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables)
         out = [[] for _ in range(B)]
         unfinished = [True] * B
         nodes = [trie.root for _ in range(B)] if trie is not None else None
@@ -263,6 +301,30 @@ class KVCacheLM:
         return out
 
     # ------------------------------------------------------------------ greedy decoding with the loop on the device
+    def _trie_tables(self, trie, eos):
+        """the device copy of `trie`, flattened; None when the trie is not eligible for the device loop.  The trie is mutable, so it is
+        flattened on every call, but uploaded only when the arrays differ from the last call's.  The device buffers persist (fixed
+        addresses under the captured graph) and grow by reallocation, which changes the graph key."""
+        cfg, dev = self.model.cfg, self.model.device
+        off, tok, nxt, eligible = flatten_trie(trie, eos, cfg.vocab_size, cfg.special_token_ids)
+        if not eligible:
+            return None
+        host = (off, tok, nxt)
+        same = self._trie_host is not None and all(a.shape == b.shape and np.array_equal(a, b) for a, b in zip(host, self._trie_host))
+        if not same:
+            t = self._trie_dev
+            if t is None or t["off"].numel() < off.size or t["tok"].numel() < tok.size:
+                grow = lambda k: max(1024, 2 * k)
+                t = {"off": torch.zeros((grow(off.size),), dtype=I32, device=dev), "tok": torch.zeros((grow(tok.size),), dtype=I32, device=dev),
+                     "nxt": torch.zeros((grow(tok.size),), dtype=I32, device=dev)}
+            up = ops.h2d(torch.from_numpy(np.concatenate(host)), dev)               # one staging buffer, one H2D copy
+            t["off"][:off.size].copy_(up[:off.size])
+            t["tok"][:tok.size].copy_(up[off.size:off.size + tok.size])
+            t["nxt"][:nxt.size].copy_(up[off.size + tok.size:])
+            t["n_nodes"] = int(off.size - 1)
+            self._trie_host, self._trie_dev = host, t
+        return self._trie_dev
+
     def _greedy_state(self, max_steps):
         """persistent buffers of the device loop (fixed addresses: the step is replayed from a hipGraph)"""
         g = self._greedy
@@ -272,7 +334,8 @@ class KVCacheLM:
         L = ops._L()
         n = L.nv_decode_state_ints(B)
         vp = m.store.vocab_pad
-        g = {"max_steps": max(max_steps, 64), "graph": None, "graph_key": None,
+        g = {"max_steps": max(max_steps, 64), "graphs": {},        # which pick (free / trie) -> (key, captured hipGraph)
+             "node": torch.zeros((B,), dtype=I32, device=dev),     # each sample's trie node (the trie pick only)
              "state": torch.zeros((n,), dtype=I32, device=dev), "hs": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev),
              "x": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev), "logits": torch.zeros((B, vp), dtype=BF16, device=dev),
              "fin_host": [torch.zeros((B,), dtype=I32).pin_memory() for _ in range(3)]}     # landing buffers of the lagging `fin` poll
@@ -280,21 +343,26 @@ class KVCacheLM:
         self._greedy = g
         return g
 
-    def _greedy_step(self, g, eos, pad, stream, dec):
-        """`dec`: the native decoder, resolved by the caller BEFORE any stream capture (nothing here may allocate or rebuild)"""
+    def _greedy_step(self, g, eos, pad, stream, dec, trie=None):
+        """`dec`: the native decoder, resolved by the caller BEFORE any stream capture (nothing here may allocate or rebuild);
+        `trie`: the device tables of `_trie_tables` -> the step picks among the children of g["node"]"""
         m, cfg, st = self.model, self.model.cfg, self.model.store
         sp = cfg.special_token_ids
-        rc = ops._L().nv_decoder_greedy_step(dec, g["hs"].data_ptr(), st.p("lang_model.model.embed_tokens.weight").data_ptr(),
-                                             st.lm_head_padded().data_ptr(), st.vocab_pad, cfg.vocab_size, sp[0], len(sp), g["logits"].data_ptr(),
-                                             g["x"].data_ptr(), g["state"].data_ptr(), g["out"].data_ptr(), g["max_steps"], self.kv0.data_ptr(),
-                                             self.attn.data_ptr(), self.lse.data_ptr(), self.B, self.cap, eos, pad, self._ws.data_ptr(),
-                                             self._ws.numel(), stream)
-        _lib.check(rc, "nv_decoder_greedy_step")
+        head = (dec, g["hs"].data_ptr(), st.p("lang_model.model.embed_tokens.weight").data_ptr(), st.lm_head_padded().data_ptr(), st.vocab_pad,
+                cfg.vocab_size, sp[0], len(sp))
+        tail = (g["logits"].data_ptr(), g["x"].data_ptr(), g["state"].data_ptr(), g["out"].data_ptr(), g["max_steps"], self.kv0.data_ptr(),
+                self.attn.data_ptr(), self.lse.data_ptr(), self.B, self.cap, eos, pad, self._ws.data_ptr(), self._ws.numel(), stream)
+        if trie is None:
+            _lib.check(ops._L().nv_decoder_greedy_step(*head, *tail), "nv_decoder_greedy_step")
+        else:
+            _lib.check(ops._L().nv_decoder_trie_step(*head, trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(), trie["n_nodes"],
+                                                     g["node"].data_ptr(), *tail), "nv_decoder_trie_step")
 
     @torch.no_grad()
-    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad):
+    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad, trie=None):
         """prefill through `extend` (host-built indices, once), then max_new_tokens replays of ONE captured step
-        (nv_decoder_greedy_step: lm_head -> masked argmax + finished/pad bookkeeping -> cache indices -> embedding -> decoder layers).
+        (nv_decoder_greedy_step: lm_head -> masked argmax + finished/pad bookkeeping -> cache indices -> embedding -> decoder layers;
+        with `trie`, the device tables of `_trie_tables`: nv_decoder_trie_step, the argmax over the children of each row's trie node).
         The host never waits for a token: it polls the `fin` flags two steps behind and trims the output where HF would have stopped."""
         B, dev = self.B, self.model.device
         g = self._greedy_state(max_new_tokens)
@@ -303,11 +371,14 @@ class KVCacheLM:
         need = L.nv_decoder_workspace_bytes(dec, B)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        if USE_HIP_GRAPH and g["graph"] is None:
+        kind = trie is not None
+        if USE_HIP_GRAPH and kind not in g["graphs"]:
             # one eager step on a scratch state BEFORE the prefill: the kernels' first-use initialisation (hipFuncSetAttribute, device
             # queries) must not happen inside a stream capture.  It writes cache row 0 of every sample, which the prefill rewrites.
             g["state"].zero_()
-            self._greedy_step(g, eos, pad, ops._st(), dec)
+            if kind:
+                g["node"].zero_()
+            self._greedy_step(g, eos, pad, ops._st(), dec, trie)
         Hs = self.extend(seqs, vix, vis_all, keys)
         assert self._decoder() is dec, "the decoder table changed between prefill and decode"
         n = g["state"].numel()
@@ -316,20 +387,23 @@ class KVCacheLM:
         g["state"].copy_(ops.h2d(torch.from_numpy(init), dev))
         g["hs"].copy_(Hs)
         key = (self._dec_key, self._ws.data_ptr(), eos, pad, g["out"].data_ptr())
-        if USE_HIP_GRAPH and g["graph_key"] != key:
+        if kind:                                               # the tables' addresses and the node count are frozen launch arguments too
+            g["node"].zero_()                                  # every row starts at the root
+            key += (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(), trie["n_nodes"], g["node"].data_ptr())
+        if USE_HIP_GRAPH and g["graphs"].get(kind, (None, None))[0] != key:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec)
-            g["graph"], g["graph_key"] = graph, key            # capture enqueues nothing: the first replay is step 0
+                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec, trie)
+            g["graphs"][kind] = (key, graph)                   # capture enqueues nothing: the first replay is step 0
         events = []
         steps = 0
         for t in range(max_new_tokens):
             if USE_HIP_GRAPH:
-                g["graph"].replay()
+                g["graphs"][kind][1].replay()
             else:
-                self._greedy_step(g, eos, pad, ops._st(), dec)
+                self._greedy_step(g, eos, pad, ops._st(), dec, trie)
             steps += 1
             if len(events) >= 2:                               # flags as of two steps ago: the host stays ahead of the GPU
                 ev, snap = events.pop(0)
