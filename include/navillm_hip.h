@@ -369,13 +369,28 @@ int nv_rope_scatter_rows_bf16(const void* qkv, const void* cos_t, const void* si
  *      current node (a buffer of its own: zero it before the first step).  nv_decode_pick_trie_bf16: the pick rule and bookkeeping of
  *      nv_decode_pick_bf16 over the children of node[b] only, then node[b] = trie_nxt[winning edge] (a finished row keeps its node).
  *      Table entries that point outside the tables are skipped, never followed; a node without a pickable child emits `eos` (the row
- *      finishes) and keeps its node.  nv_decoder_trie_step: nv_decoder_greedy_step with that pick. */
+ *      finishes) and keeps its node.  nv_decoder_trie_step: nv_decoder_greedy_step with that pick.
+ *      Sampled form (HF sample(): mask -> trie -> / temperature -> top-k -> softmax -> one draw per row).  nv_decode_pick_sample_bf16:
+ *      the candidates of row b are the pickable ids < V, or (trie arguments non-null; all null / 0 together otherwise) the pickable
+ *      children of node[b]; a NaN logit is no candidate.  top_k > 0 keeps every candidate >= the top_k-th largest candidate logit
+ *      (ties at the threshold included; 0 or >= the number of candidates keeps all, there is no upper limit).  Weights
+ *      exp((x - max) / temperature) in fp32.  rng: two DEVICE words {seed, offset} (device memory, because a captured graph freezes
+ *      launch arguments); the draw of row b at step cnt = state[7B+2] is word 0 of Philox4x32-10 at counter offset + cnt*B + b, key
+ *      seed (the convention of nv_dropout_f32), u = (word >> 8) * 2^-24 + 2^-25.  The pick is the kept candidate with the smallest id
+ *      whose running sum of weights, in ascending id order, exceeds u * total (past the end: the last one with weight > 0); the
+ *      summation order is fixed, so equal (logits, rng, cnt) give equal tokens.  The bookkeeping and the move along the picked edge
+ *      are those of the two picks above; a row with no kept candidate of non-zero weight emits `eos` and keeps its node.  u_out
+ *      (nullable): u_out[cnt*B + b] = u while cnt < max_steps.  NV_ERR_ARG: temperature not finite and > 0, top_k < 0, partly-null
+ *      trie arguments.  nv_decoder_sample_step: nv_decoder_greedy_step with that pick (trie arguments nullable). */
 int nv_decode_state_ints(int B);
 int nv_decode_pick_bf16(const void* logits, int ldl, int V, int special0, int nspecial, int* state, int* out, int max_steps, int B, int eos,
                         int pad, void* stream);
 int nv_decode_pick_trie_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
                              const int* trie_nxt, int n_nodes, int* node, int* state, int* out, int max_steps, int B, int eos, int pad,
                              void* stream);
+int nv_decode_pick_sample_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                               const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, const unsigned long long* rng,
+                               float* u_out, int* state, int* out, int max_steps, int B, int eos, int pad, void* stream);
 int nv_decode_advance(int* state, int B, int cap, void* stream);
 int nv_decoder_greedy_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B,
@@ -384,6 +399,10 @@ int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const
                          const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, void* logits, void* x,
                          int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
                          void* workspace, size_t workspace_bytes, void* stream);
+int nv_decoder_sample_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
+                           const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
+                           const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
+                           void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- data-parallel exchange over RCCL (C0-C3): replaces the DDP gradient all-reduce behind tools/optims.py:52-54
  *      (+ its initial parameter broadcast) and the task-id broadcast of tasks/loaders.py:176-179.

@@ -5,13 +5,14 @@
 // sync, the python index bookkeeping and an upload.  Here the choice and the bookkeeping are two tiny kernels, so a whole step
 // (lm_head -> pick -> advance -> embed -> 32 decoder layers) has frozen launch arguments and is replayed from a hipGraph
 // (navillm_amd/kvcache.py); the host only polls the `fin` flags, a step or two behind.
+// Sampled decoding (HF sample(): temperature, top-k, one draw per row) is the same step with decode_pick_sample_kernel as its pick.
 //
 // state layout (int32, one buffer): tok[B] | fin[B] | len[B] | pos[B] | crow[B] | grow[B] | last[B] | dyn[2] | cnt[1] | overflow[1]
 #include "nv_common.h"
 
 namespace {
 
-// ---- what the two pick kernels share: the pick rule, the block reduction and HF's bookkeeping
+// ---- what the pick kernels share: the pick rule, the block reduction and HF's bookkeeping
 constexpr int PICK_NONE = 0x7fffffff;                             // "no candidate yet"
 
 // a candidate id is pickable when it lies inside the vocabulary and outside the special range (models/modified_lm.py:122-124)
@@ -135,6 +136,167 @@ __global__ __launch_bounds__(TRIE_T) void decode_pick_trie_kernel(const bf16_t* 
     }
 }
 
+// ---- sampled decoding (HF sample() as the host loop of kvcache.py restates it: mask -> trie -> / temperature -> top-k -> softmax ->
+// one draw per row).  Grid B, 1024 threads.  The ITEMS of row b are the ids [0, V) (TRIE = false) or the edges of node[b], which are
+// sorted by token id (TRIE = true, with the bounds handling of decode_pick_trie_kernel); an item is a CANDIDATE when its id passes
+// pick_allowed and its logit is no NaN.
+//   top-k   x_k = the top_k-th largest candidate logit (with multiplicity); every candidate >= x_k is kept (ties at the threshold
+//           included, as `lg < kth` does on the host); top_k == 0 or >= the number of candidates keeps them all.  Logits are bf16, so
+//           x_k is found exactly by a two-pass radix select over the order-preserving 16-bit key: two 256-bin LDS histograms, no sort.
+//   weight  w = exp((x - m) / T) in fp32, m = the largest candidate logit (always kept): the total is >= 1; w(-inf) = 0.
+//   draw    u = philox_u01(word 0 of Philox counter rng[1] + cnt*B + b, key rng[0]); the pick is the first kept item whose running sum
+//           of weights, in item order, exceeds u * total -- past the end (rounding): the last kept item with w > 0.  Each thread owns
+//           a contiguous item range and sums it in order; a block scan of the 1024 sums gives every range its start.  The order is
+//           fixed, so equal (logits, rng, cnt) give equal tokens, eager or replayed.
+// The four passes re-read the row (64 KB at V = 32 000: L2-resident right after the lm_head wrote it); the two histogram passes
+// stride over the items, the two summing passes walk each thread's own range.  A row without a kept candidate of non-zero weight
+// emits `eos` and keeps its node.  Nothing outside logits[b, 0..V), the tables and state/out/u_out[cnt*B + b] is touched.
+constexpr int SAMP_T = 1024;
+// inclusive scan over the SAMP_T threads (in each wave, then over the 16 wave totals in wave order); `total` to every thread
+template <typename T>
+__device__ __forceinline__ T samp_scan(T v, T& total) {
+    __shared__ T ws[SAMP_T / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(v, o, 64);
+        if (lane >= o) v += y;
+    }
+    __syncthreads();                                                  // (the readers of an earlier scan are done with ws)
+    if (lane == 63) ws[w] = v;
+    __syncthreads();
+    T base = 0;
+    total = 0;
+#pragma unroll
+    for (int j = 0; j < SAMP_T / 64; ++j) {
+        if (j < w) base += ws[j];
+        total += ws[j];
+    }
+    return base + v;
+}
+// the bin of a 256-bin histogram that holds the k-th largest entry (1 <= k <= the histogram's total), and k's rank inside that bin
+__device__ __forceinline__ void samp_select(const int* hist, int k, int* bin, int* rank, int& total) {
+    const int tid = threadIdx.x;
+    const int c = tid < 256 ? hist[255 - tid] : 0;                    // thread t holds bin 255 - t: the scan counts from the top
+    const int above = samp_scan<int>(c, total) - c;
+    if (tid < 256 && above < k && above + c >= k) { *bin = 255 - tid; *rank = k - above; }
+    __syncthreads();
+}
+template <bool TRIE>
+__global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t* __restrict__ logits, int ldl, int V, int special0,
+                                                                    int nspecial, const int* __restrict__ toff, const int* __restrict__ ttok,
+                                                                    const int* __restrict__ tnxt, int n_nodes, int* __restrict__ node,
+                                                                    float temperature, int top_k, const uint64_t* __restrict__ rng,
+                                                                    float* __restrict__ u_out, int* __restrict__ state, int* __restrict__ out,
+                                                                    int max_steps, int B, int eos, int pad) {
+    __shared__ int hist[2][256];
+    __shared__ int s_bin[2], s_rank[2], s_max, s_first, s_last;
+    __shared__ float s_u;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bf16_t* row = logits + (long)b * ldl;
+    if (tid == 0) {
+        const int cnt = state[7 * B + 2];
+        const uint64_t ctr = rng[1] + (uint64_t)(long)cnt * (uint64_t)B + (uint64_t)b;
+        uint32_t r[4];
+        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)rng[0], (uint32_t)(rng[0] >> 32), r);
+        s_u = philox_u01(r[0]);
+        if (u_out && cnt >= 0 && cnt < max_steps) u_out[(long)cnt * B + b] = s_u;
+        s_max = -1; s_first = PICK_NONE; s_last = -1;
+        s_bin[0] = s_bin[1] = 0; s_rank[0] = s_rank[1] = 0;
+    }
+    if (state[B + b] != 0) {                                          // a finished row emits `pad` whatever it would draw (fin[b] is
+        if (tid == 0) pick_emit(state, out, max_steps, B, b, pad, eos, pad);   // written by this block's thread 0 alone)
+        return;
+    }
+    int e0 = 0, n = V;
+    if (TRIE) {
+        const int nd = node[b];
+        int e1 = 0;
+        if (nd >= 0 && nd < n_nodes) {
+            const int E = toff[n_nodes];
+            e0 = max(toff[nd], 0);
+            e1 = min(toff[nd + 1], E);
+        }
+        n = max(e1 - e0, 0);
+    }
+    // item i -> its id v and the order-preserving key of its logit (larger logit <=> larger key; -0 counts as +0), -1: no candidate
+    auto key_of = [&](int i, int& v) -> int {
+        v = TRIE ? ttok[e0 + i] : i;
+        if (v < 0 || !pick_allowed(v, V, special0, nspecial)) return -1;
+        uint32_t h = row[v];
+        if ((h & 0x7fffu) > 0x7f80u) return -1;                       // NaN
+        if (h == 0x8000u) h = 0;
+        return (int)((h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u));
+    };
+    auto logit_of = [](int key) -> float { return bf2f((bf16_t)((key & 0x8000) ? (key & 0x7fff) : (~key & 0xffff))); };
+    if (tid < 256) hist[0][tid] = hist[1][tid] = 0;
+    __syncthreads();
+    // pass 1: the histogram of the keys' high bytes, the number of candidates and the largest key
+    int v, kmax = -1;
+    for (int i = tid; i < n; i += SAMP_T) {
+        const int k = key_of(i, v);
+        if (k < 0) continue;
+        atomicAdd(&hist[0][k >> 8], 1);
+        kmax = max(kmax, k);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) kmax = max(kmax, __shfl_xor(kmax, o, 64));
+    if ((tid & 63) == 0) atomicMax(&s_max, kmax);
+    __syncthreads();
+    int ncand, dummy;
+    const int want = top_k > 0 ? top_k : 0x7fffffff;
+    samp_select(hist[0], want, &s_bin[0], &s_rank[0], ncand);        // (selects nothing when want > ncand)
+    int thr = 0;                                                      // the smallest kept key
+    if (want < ncand) {
+        // pass 2: the low bytes of the keys that share the threshold's high byte
+        const int hb = s_bin[0];
+        for (int i = tid; i < n; i += SAMP_T) {
+            const int k = key_of(i, v);
+            if (k >= 0 && (k >> 8) == hb) atomicAdd(&hist[1][k & 255], 1);
+        }
+        __syncthreads();
+        samp_select(hist[1], s_rank[0], &s_bin[1], &s_rank[1], dummy);
+        thr = (hb << 8) | s_bin[1];
+    }
+    const float m = logit_of(max(s_max, 0)), T = temperature;
+    auto weight_of = [&](int k) -> float {
+        if (k < thr) return 0.f;
+        const float x = logit_of(k);
+        return x == -INFINITY ? 0.f : x == m ? 1.f : expf((x - m) / T);
+    };
+    // pass 3: each thread sums the weights of its own contiguous items, in order
+    const int per = (n + SAMP_T - 1) / SAMP_T;
+    const int i0 = (int)min((long)tid * per, (long)n), i1 = (int)min((long)i0 + per, (long)n);
+    float mine = 0.f;
+    for (int i = i0; i < i1; ++i) mine += weight_of(key_of(i, v));
+    float total;
+    float run = samp_scan<float>(mine, total) - mine;                 // the running sum in front of item i0
+    // pass 4: the same sums again, against u * total
+    const float target = s_u * total;
+    int first = PICK_NONE, last = -1;
+    for (int i = i0; i < i1; ++i) {
+        const float w = weight_of(key_of(i, v));
+        if (w > 0.f) {
+            run += w;
+            last = i;
+            if (first == PICK_NONE && run > target) first = i;
+        }
+    }
+    if (first != PICK_NONE) atomicMin(&s_first, first);
+    if (last >= 0) atomicMax(&s_last, last);
+    __syncthreads();
+    if (tid == 0) {
+        const int i = s_first != PICK_NONE ? s_first : s_last;
+        const bool none = i < 0;
+        if (!none) key_of(i, v);
+        pick_emit(state, out, max_steps, B, b, none ? eos : v, eos, pad);
+        if (TRIE && !none) {
+            const int nx = tnxt[e0 + i];
+            if (nx >= 0 && nx < n_nodes) node[b] = nx;
+        }
+    }
+}
+
 // one block: the token picked for sample b goes to cache row b*cap + len[b] at position len[b]; dyn = {max len + 1, 128-aligned
 // first query row}; len += 1; cnt += 1.  A full cache (len == cap) sends the row to the junk row B*cap, stops growing, marks the sample
 // FINISHED (it emits `pad` from the next step on: its query would be read back from the shared junk row, i.e. be garbage) and
@@ -197,6 +359,24 @@ int nv_decode_pick_trie_bf16(const void* logits, int ldl, int V, int special0, i
     if (B <= 0 || V <= 0 || ldl < V || n_nodes <= 0 || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
     NV_LAUNCH(decode_pick_trie_kernel, dim3(B), dim3(TRIE_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0, nspecial,
               trie_off, trie_tok, trie_nxt, n_nodes, node, state, out, max_steps, B, eos, pad);
+    return nv_check_launch();
+}
+
+int nv_decode_pick_sample_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                               const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, const unsigned long long* rng,
+                               float* u_out, int* state, int* out, int max_steps, int B, int eos, int pad, void* stream) {
+    if (!logits || !rng || !state || !out || B <= 0 || V <= 0 || ldl < V || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
+    if (!(temperature > 0.f && temperature <= 3.402823466e38f) || top_k < 0) return NV_ERR_ARG;      // (a NaN fails both comparisons)
+    const bool trie = trie_off || trie_tok || trie_nxt || node || n_nodes != 0;
+    if (trie && (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0)) return NV_ERR_ARG;
+    if (trie)
+        NV_LAUNCH(decode_pick_sample_kernel<true>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
+                  nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, (const uint64_t*)rng, u_out, state, out, max_steps,
+                  B, eos, pad);
+    else
+        NV_LAUNCH(decode_pick_sample_kernel<false>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
+                  nspecial, nullptr, nullptr, nullptr, 0, nullptr, temperature, top_k, (const uint64_t*)rng, u_out, state, out, max_steps, B,
+                  eos, pad);
     return nv_check_launch();
 }
 

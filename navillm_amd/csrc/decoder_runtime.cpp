@@ -318,11 +318,13 @@ int nv_decoder_extend(const nv_decoder* p, const void* x_in, const int* pos, con
 //   hs [B,d] in/out;  embed [V.., d];  lm_head [Vp, d] (rows >= V unused);  logits [B, Vp] bf16 scratch;  x [B, d] scratch;
 //   state: nv_decode_state_ints(B) ints (tok|fin|len|pos|crow|grow|last|dyn|cnt);  out [max_steps, B] picked tokens
 // nv_decoder_trie_step is the same step with the argmax taken over the children of each sample's trie node (node [B], moved along
-// the picked edge); both are decode_step() below, `node == nullptr` selecting the unconstrained pick.
+// the picked edge); nv_decoder_sample_step draws the token instead (nv_decode_pick_sample_bf16: temperature, top-k, one Philox draw
+// per row keyed by the device words rng = {seed, offset}), over the vocabulary or over the node's children.  All three are
+// decode_step() below: `node == nullptr` selects the unconstrained candidates, `rng == nullptr` the argmax.
 static int decode_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
-                       const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, void* logits, void* x,
-                       int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
-                       void* workspace, size_t workspace_bytes, void* stream) {
+                       const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
+                       const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
+                       void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !hs || !embed || !lm_head || !logits || !x || !state || !out || !kv0 || !attn_buf || !lse || !workspace) return NV_ERR_ARG;
     if (B <= 0 || Vp < V || V <= 0) return NV_ERR_ARG;
     const int d = p->d;
@@ -330,7 +332,9 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
     if (B <= 16 && (d & 31) == 0) rc = nv_gemv_bf16(hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, stream);
     else rc = nv_gemm_bf16_ws(0, hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, 0, p->gemm_ws, stream);
     if (rc != NV_OK) return rc;
-    if (node) rc = nv_decode_pick_trie_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out,
+    if (rng) rc = nv_decode_pick_sample_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k,
+                                             rng, nullptr, state, out, max_steps, B, eos, pad, stream);
+    else if (node) rc = nv_decode_pick_trie_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out,
                                             max_steps, B, eos, pad, stream);
     else rc = nv_decode_pick_bf16(logits, Vp, V, special0, nspecial, state, out, max_steps, B, eos, pad, stream);
     if (rc != NV_OK) return rc;
@@ -344,8 +348,8 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
 int nv_decoder_greedy_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B,
                            int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, logits, x, state, out,
-                       max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, nullptr, logits, x, state,
+                       out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
 int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
@@ -353,8 +357,17 @@ int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const
                          int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0) return NV_ERR_ARG;
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, logits, x, state, out,
-                       max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0.f, 0, nullptr, logits, x,
+                       state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+}
+
+int nv_decoder_sample_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
+                           const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
+                           const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
+                           void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!rng) return NV_ERR_ARG;                  // (the trie arguments, temperature and top_k are checked by the pick)
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, rng,
+                       logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -146,6 +146,22 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
+// ---- Philox4x32-10: the counter-based RNG of the dropout kernels (enc_f32.hip) and of sampled decoding (decode_step.hip) ----
+// Convention of every user: counter n -> c0/c1 = its low/high word, c2 = c3 = 0; key = the low/high word of the seed.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// one output word -> a uniform in (0, 1]: the top 24 bits at the centre of their 2^-24 cell.  Exact in fp32 below 0.5; above, the
+// 25-bit sum rounds to even (the product is exact, so mul + add and fma agree) and the topmost cell gives 1.0 -- never 0.
+__device__ __forceinline__ float philox_u01(uint32_t word) { return (float)(word >> 8) * (1.0f / 16777216.0f) + (1.0f / 33554432.0f); }
+
 // XCD-aware, bijective block-id remap (8 XCDs, block b runs on XCD b%8): give each XCD a
 // contiguous chunk of tile ids so neighbouring tiles share an L2.
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

@@ -8,6 +8,7 @@ Two callers:
 * **greedy generation** (`KVCacheLM.generate`): HF `generate(do_sample=False)` as the reference calls it
   (models/nav_model.py:324-341,388-402; models/modified_lm.py:184-199) with the special-id logit mask
   (modified_lm.py:122-124) and the trie-constrained decoding of modified_lm.py:10-30.
+  `do_sample=True` (tasks/agents/llava.py:58-62) samples instead: on the host loop, or -- NAVILLM_DEVICE_SAMPLE=1 -- in the same device loop.
 
 Layout: one packed post-RoPE `qkv` buffer per decoder layer, `[B*capacity (+1 junk row), 3d]` bf16 (7B, B=8,
 capacity 1024: 201 MB per layer, 6.4 GB in all -- nothing next to 288 GB).  Samples are LEFT-aligned (token j of
@@ -20,6 +21,7 @@ Everything arithmetic is a launch of the same HIP kernels as the training path (
 `nv_attn_fwd_strided_bf16`); there is no autograd here.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -28,10 +30,14 @@ import torch
 from . import lib as _lib
 from . import ops
 from . import debug as _debug
+from . import functions as _fn
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 DEVICE_GREEDY = os.environ.get("NAVILLM_DEVICE_GREEDY", "1") != "0"      # greedy decoding (free or trie-constrained) with the loop on the device
 USE_HIP_GRAPH = os.environ.get("NAVILLM_DECODE_GRAPH", "1") != "0"       # ... replayed from a captured hipGraph
+# do_sample=True with the loop on the device as well.  Opt-in: the draws then come from the library's own Philox4x32-10 (keyed from
+# torch's CUDA generator like the dropout kernels), which cannot reproduce torch.multinomial's stream draw for draw.
+DEVICE_SAMPLE = os.environ.get("NAVILLM_DEVICE_SAMPLE", "0") != "0"
 
 
 def flatten_trie(trie, eos, V, special_ids):
@@ -81,6 +87,7 @@ class KVCacheLM:
         self._greedy = None                                    # device-side decode loop: buffers + captured hipGraphs
         self._trie_host, self._trie_dev = None, None           # the flattened trie of the last constrained call, host and device
         self.last_generate = None                              # {"loop": "device" | "host", "trie": bool} of the last generate()
+        self.last_sample = None                                # {"seed", "offset", "temperature", "top_k"} of a device-sampled generate()
         self._key_ids = {}                                     # reuse key (hashable) -> small int
         self.reset()
 
@@ -254,6 +261,10 @@ class KVCacheLM:
         do_sample=True (tasks/agents/llava.py:58-62 forwards `--do_sample --temperature`): HF's `sample()` -- after the mask and
         the trie, logits / temperature, the default top-k (50) warper, softmax, one multinomial draw per row from torch's CUDA
         generator (same distribution as the reference; the streams of two RNG implementations cannot be compared draw by draw).
+        With NAVILLM_DEVICE_SAMPLE=1 a sampled call runs the device loop too (temperature finite and > 0, top_k None or an int >= 0,
+        room in the cache, an eligible trie; anything else keeps the host loop): the same distribution, drawn by
+        `decode_pick_sample_kernel` from Philox counters taken from torch's CUDA generator (`torch.manual_seed` makes a run
+        reproducible); `last_sample` then records the seed, the offset and the two settings.
         Returns B lists with the new tokens only."""
         B = self.B
         self.reset()
@@ -261,11 +272,24 @@ class KVCacheLM:
         vix = None if vis_idx_list is None else [list(v) for v in vis_idx_list]
         keys = None if vis_all is None else [("gen", r) for r in range(vis_all.shape[0])]   # constant within one call
         self.last_generate = {"loop": "host", "trie": trie is not None}
-        if not do_sample and DEVICE_GREEDY and max_new_tokens > 0 and max(len(x) for x in seqs) + max_new_tokens <= self.cap:
+        self.last_sample = None
+        if do_sample:
+            on_device = (DEVICE_SAMPLE and isinstance(temperature, (int, float)) and math.isfinite(temperature)
+                         and 0.0 < float(np.float32(temperature)) < math.inf                   # (what the kernel is handed is an fp32)
+                         and (top_k is None or (isinstance(top_k, int) and top_k >= 0)))
+        else:
+            on_device = DEVICE_GREEDY
+        if on_device and max_new_tokens > 0 and max(len(x) for x in seqs) + max_new_tokens <= self.cap:
             tables = None if trie is None else self._trie_tables(trie, eos_token_id)
             if trie is None or tables is not None:                 # (an ineligible trie keeps the host loop)
                 self.last_generate["loop"] = "device"
-                return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables)
+                sampler = None
+                if do_sample:                                      # one Philox counter per draw, accounted like the attention-probability dropout
+                    seed, offset = _fn._philox_take(self.model.device, 4 * B * max_new_tokens)
+                    sampler = {"seed": int(seed), "offset": int(offset), "temperature": float(temperature),
+                               "top_k": min(int(top_k or 0), 2 ** 31 - 1)}
+                    self.last_sample = dict(sampler)
+                return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables, sampler)
         out = [[] for _ in range(B)]
         unfinished = [True] * B
         nodes = [trie.root for _ in range(B)] if trie is not None else None
@@ -300,7 +324,7 @@ class KVCacheLM:
                 break
         return out
 
-    # ------------------------------------------------------------------ greedy decoding with the loop on the device
+    # ------------------------------------------------------------------ decoding (greedy or sampled) with the loop on the device
     def _trie_tables(self, trie, eos):
         """the device copy of `trie`, flattened; None when the trie is not eligible for the device loop.  The trie is mutable, so it is
         flattened on every call, but uploaded only when the arrays differ from the last call's.  The device buffers persist (fixed
@@ -336,6 +360,7 @@ class KVCacheLM:
         vp = m.store.vocab_pad
         g = {"max_steps": max(max_steps, 64), "graphs": {},        # which pick (free / trie) -> (key, captured hipGraph)
              "node": torch.zeros((B,), dtype=I32, device=dev),     # each sample's trie node (the trie pick only)
+             "rng": torch.zeros((2,), dtype=torch.int64, device=dev),   # {seed, offset} of the sampled pick: changes per call, so not a launch argument
              "state": torch.zeros((n,), dtype=I32, device=dev), "hs": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev),
              "x": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev), "logits": torch.zeros((B, vp), dtype=BF16, device=dev),
              "fin_host": [torch.zeros((B,), dtype=I32).pin_memory() for _ in range(3)]}     # landing buffers of the lagging `fin` poll
@@ -343,26 +368,32 @@ class KVCacheLM:
         self._greedy = g
         return g
 
-    def _greedy_step(self, g, eos, pad, stream, dec, trie=None):
+    def _greedy_step(self, g, eos, pad, stream, dec, trie=None, sampler=None):
         """`dec`: the native decoder, resolved by the caller BEFORE any stream capture (nothing here may allocate or rebuild);
-        `trie`: the device tables of `_trie_tables` -> the step picks among the children of g["node"]"""
+        `trie`: the device tables of `_trie_tables` -> the step picks among the children of g["node"];
+        `sampler`: temperature and top_k -> the step draws its token, keyed by the two words in g["rng"]"""
         m, cfg, st = self.model, self.model.cfg, self.model.store
         sp = cfg.special_token_ids
         head = (dec, g["hs"].data_ptr(), st.p("lang_model.model.embed_tokens.weight").data_ptr(), st.lm_head_padded().data_ptr(), st.vocab_pad,
                 cfg.vocab_size, sp[0], len(sp))
         tail = (g["logits"].data_ptr(), g["x"].data_ptr(), g["state"].data_ptr(), g["out"].data_ptr(), g["max_steps"], self.kv0.data_ptr(),
                 self.attn.data_ptr(), self.lse.data_ptr(), self.B, self.cap, eos, pad, self._ws.data_ptr(), self._ws.numel(), stream)
-        if trie is None:
+        tr = (None, None, None, 0, None) if trie is None else (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(),
+                                                               trie["n_nodes"], g["node"].data_ptr())
+        if sampler is not None:
+            _lib.check(ops._L().nv_decoder_sample_step(*head, *tr, sampler["temperature"], sampler["top_k"], g["rng"].data_ptr(), *tail),
+                       "nv_decoder_sample_step")
+        elif trie is None:
             _lib.check(ops._L().nv_decoder_greedy_step(*head, *tail), "nv_decoder_greedy_step")
         else:
-            _lib.check(ops._L().nv_decoder_trie_step(*head, trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(), trie["n_nodes"],
-                                                     g["node"].data_ptr(), *tail), "nv_decoder_trie_step")
+            _lib.check(ops._L().nv_decoder_trie_step(*head, *tr, *tail), "nv_decoder_trie_step")
 
     @torch.no_grad()
-    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad, trie=None):
+    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad, trie=None, sampler=None):
         """prefill through `extend` (host-built indices, once), then max_new_tokens replays of ONE captured step
         (nv_decoder_greedy_step: lm_head -> masked argmax + finished/pad bookkeeping -> cache indices -> embedding -> decoder layers;
-        with `trie`, the device tables of `_trie_tables`: nv_decoder_trie_step, the argmax over the children of each row's trie node).
+        with `trie`, the device tables of `_trie_tables`: nv_decoder_trie_step, the argmax over the children of each row's trie node;
+        with `sampler`: nv_decoder_sample_step, a draw among the same candidates).
         The host never waits for a token: it polls the `fin` flags two steps behind and trims the output where HF would have stopped."""
         B, dev = self.B, self.model.device
         g = self._greedy_state(max_new_tokens)
@@ -371,14 +402,16 @@ class KVCacheLM:
         need = L.nv_decoder_workspace_bytes(dec, B)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        kind = trie is not None
+        kind = trie is not None                                # which captured graph: free / trie, and ("sample", free / trie)
+        if sampler is not None:
+            kind = ("sample", kind)
         if USE_HIP_GRAPH and kind not in g["graphs"]:
             # one eager step on a scratch state BEFORE the prefill: the kernels' first-use initialisation (hipFuncSetAttribute, device
             # queries) must not happen inside a stream capture.  It writes cache row 0 of every sample, which the prefill rewrites.
             g["state"].zero_()
-            if kind:
+            if trie is not None:
                 g["node"].zero_()
-            self._greedy_step(g, eos, pad, ops._st(), dec, trie)
+            self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler)
         Hs = self.extend(seqs, vix, vis_all, keys)
         assert self._decoder() is dec, "the decoder table changed between prefill and decode"
         n = g["state"].numel()
@@ -387,15 +420,19 @@ class KVCacheLM:
         g["state"].copy_(ops.h2d(torch.from_numpy(init), dev))
         g["hs"].copy_(Hs)
         key = (self._dec_key, self._ws.data_ptr(), eos, pad, g["out"].data_ptr())
-        if kind:                                               # the tables' addresses and the node count are frozen launch arguments too
+        if trie is not None:                                   # the tables' addresses and the node count are frozen launch arguments too
             g["node"].zero_()                                  # every row starts at the root
             key += (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(), trie["n_nodes"], g["node"].data_ptr())
+        if sampler is not None:                                # so are the two settings; the seed and the offset travel through g["rng"]
+            key += (sampler["temperature"], sampler["top_k"], g["rng"].data_ptr())
+            words = np.array([sampler["seed"], sampler["offset"]], dtype=np.uint64).view(np.int64)
+            g["rng"].copy_(ops.h2d(torch.from_numpy(words), dev))
         if USE_HIP_GRAPH and g["graphs"].get(kind, (None, None))[0] != key:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec, trie)
+                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec, trie, sampler)
             g["graphs"][kind] = (key, graph)                   # capture enqueues nothing: the first replay is step 0
         events = []
         steps = 0
@@ -403,7 +440,7 @@ class KVCacheLM:
             if USE_HIP_GRAPH:
                 g["graphs"][kind][1].replay()
             else:
-                self._greedy_step(g, eos, pad, ops._st(), dec, trie)
+                self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler)
             steps += 1
             if len(events) >= 2:                               # flags as of two steps ago: the host stays ahead of the GPU
                 ev, snap = events.pop(0)

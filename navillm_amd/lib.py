@@ -119,9 +119,12 @@ SIGNATURES = {
     "nv_decode_state_ints": (i, [i]),
     "nv_decode_pick_bf16": (i, [vp, i, i, i, i, ip, ip, i, i, i, i, vp]),
     "nv_decode_pick_trie_bf16": (i, [vp, i, i, i, i, ip, ip, ip, i, ip, ip, ip, i, i, i, i, vp]),
+    "nv_decode_pick_sample_bf16": (i, [vp, i, i, i, i, ip, ip, ip, i, ip, f, i, vp, fp, ip, ip, i, i, i, i, vp]),
     "nv_decode_advance": (i, [ip, i, i, vp]),
     "nv_decoder_greedy_step": (i, [vp, vp, vp, vp, i, i, i, i, vp, vp, ip, ip, i, ip, vp, fp, i, i, i, i, vp, sz, vp]),
     "nv_decoder_trie_step": (i, [vp, vp, vp, vp, i, i, i, i, ip, ip, ip, i, ip, vp, vp, ip, ip, i, ip, vp, fp, i, i, i, i, vp, sz, vp]),
+    "nv_decoder_sample_step": (i, [vp, vp, vp, vp, i, i, i, i, ip, ip, ip, i, ip, f, i, vp, vp, vp, ip, ip, i, ip, vp, fp, i, i, i, i, vp, sz,
+                                   vp]),
     # data-parallel exchange over RCCL (nv_ctx* travels as void*)
     "nv_comm_unique_id_bytes": (i, []),
     "nv_comm_unique_id": (i, [vp]),

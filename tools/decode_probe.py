@@ -3,7 +3,10 @@ prompt, then N single-token steps through the K/V cache -- host loop (token choi
 (eager) vs device loop replayed from a hipGraph (navillm_amd/kvcache.py).
 --trie[=WORDS,DEPTH] (default 2000,24): the same three loops under a trie constraint -- WORDS random words of DEPTH tokens each, about
 half of them branching off an earlier word, so every row decodes DEPTH tokens and then eos.  --reps=R timed calls per loop (default 2;
-the last one is reported, with the spread over all but the first); --free with --trie: the unconstrained loops as well."""
+the last one is reported, with the spread over all but the first); --free with --trie: the unconstrained loops as well.
+--sample [--temperature=T --top-k=K] (defaults 0.01 and 50: the reference's evaluation scripts run --do_sample --temperature 0.01):
+generate(do_sample=True) instead, host loop (torch topk / softmax / multinomial per token) vs the device loop of NAVILLM_DEVICE_SAMPLE;
+combines with --trie, --small and --free."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from navillm_amd import config as nvcfg
@@ -60,6 +63,9 @@ reps = int(opt("reps", 2))
 L, N = int(opt("prompt", 600)), 64
 g = torch.Generator().manual_seed(0)
 ids = [[1] + torch.randint(3, cfg.base_vocab_size, (L - 1 + b,), generator=g).tolist() for b in range(B)]
+sample = None
+if "--sample" in sys.argv:
+    sample = dict(do_sample=True, temperature=float(opt("temperature", 0.01)), top_k=int(opt("top-k", 50)))
 trie, eos = None, -1
 if any(a == "--trie" or a.startswith("--trie=") for a in sys.argv):
     n_words, depth = (int(x) for x in opt("trie", "2000,24").split(","))
@@ -71,17 +77,17 @@ kv = KVCacheLM(model, B, capacity=1024)
 kv.extend([list(x) for x in ids]); torch.cuda.synchronize()
 t0 = time.perf_counter(); kv.reset(); kv.extend([list(x) for x in ids]); torch.cuda.synchronize(); tp = time.perf_counter() - t0
 name = "gpt2-small-shaped" if small else "13b" if "--13b" in sys.argv else "7b"
-print(f"{name}{' fp8' if '--fp8' in sys.argv else ''}{' trie' if trie is not None else ''}: prefill {B}x~{L}: {tp*1e3:.1f} ms")
+print(f"{name}{' fp8' if '--fp8' in sys.argv else ''}{' trie' if trie is not None else ''}{f' sampled {sample}' if sample else ''}: prefill {B}x~{L}: {tp*1e3:.1f} ms")
 
 
 def measure(trie, eos, N):
     print(f"  {'trie-constrained' if trie is not None else 'unconstrained'}, {N} new tokens:")
     for tag, devloop, graph in (("host loop", False, False), ("device loop, eager", True, False), ("device loop, hipGraph", True, True)):
-        kvm.DEVICE_GREEDY, kvm.USE_HIP_GRAPH = devloop, graph
+        kvm.DEVICE_GREEDY, kvm.DEVICE_SAMPLE, kvm.USE_HIP_GRAPH = devloop, devloop, graph
         pers = []
         for rep in range(reps):
             torch.cuda.synchronize(); t0 = time.perf_counter()
-            kw = {} if trie is None else {"trie": trie}
+            kw = dict(sample or {}, **({} if trie is None else {"trie": trie}))
             out = kv.generate(ids, max_new_tokens=N, eos_token_id=eos, pad_token_id=0, **kw)
             torch.cuda.synchronize(); dt = time.perf_counter() - t0
             pers.append((dt - tp) / len(out[0]))
