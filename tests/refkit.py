@@ -66,7 +66,7 @@ def gamma(n):
 
 
 def _ibits(t):
-    return t.view(torch.int16 if t.element_size() == 2 else (torch.int32 if t.element_size() == 4 else torch.int64))
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}.get(t.element_size(), torch.int64))
 
 
 def bits_equal(a, b):
