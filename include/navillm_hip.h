@@ -381,7 +381,8 @@ int nv_rope_scatter_rows_bf16(const void* qkv, const void* cos_t, const void* si
  *      summation order is fixed, so equal (logits, rng, cnt) give equal tokens.  The bookkeeping and the move along the picked edge
  *      are those of the two picks above; a row with no kept candidate of non-zero weight emits `eos` and keeps its node.  u_out
  *      (nullable): u_out[cnt*B + b] = u while cnt < max_steps.  NV_ERR_ARG: temperature not finite and > 0, top_k < 0, partly-null
- *      trie arguments.  nv_decoder_sample_step: nv_decoder_greedy_step with that pick (trie arguments nullable). */
+ *      trie arguments.  nv_decoder_sample_step: nv_decoder_greedy_step with that pick (trie arguments nullable).
+ *      The top-p warper on top of it: include/navillm_hip_topp.h. */
 int nv_decode_state_ints(int B);
 int nv_decode_pick_bf16(const void* logits, int ldl, int V, int special0, int nspecial, int* state, int* out, int max_steps, int B, int eos,
                         int pad, void* stream);

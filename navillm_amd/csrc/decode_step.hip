@@ -5,7 +5,7 @@
 // sync, the python index bookkeeping and an upload.  Here the choice and the bookkeeping are two tiny kernels, so a whole step
 // (lm_head -> pick -> advance -> embed -> 32 decoder layers) has frozen launch arguments and is replayed from a hipGraph
 // (navillm_amd/kvcache.py); the host only polls the `fin` flags, a step or two behind.
-// Sampled decoding (HF sample(): temperature, top-k, one draw per row) is the same step with decode_pick_sample_kernel as its pick.
+// Sampled decoding (HF sample(): temperature, top-k, top-p, one draw per row) is the same step with decode_pick_sample_kernel as its pick.
 //
 // state layout (int32, one buffer): tok[B] | fin[B] | len[B] | pos[B] | crow[B] | grow[B] | last[B] | dyn[2] | cnt[1] | overflow[1]
 #include "nv_common.h"
@@ -136,21 +136,31 @@ __global__ __launch_bounds__(TRIE_T) void decode_pick_trie_kernel(const bf16_t* 
     }
 }
 
-// ---- sampled decoding (HF sample() as the host loop of kvcache.py restates it: mask -> trie -> / temperature -> top-k -> softmax ->
-// one draw per row).  Grid B, 1024 threads.  The ITEMS of row b are the ids [0, V) (TRIE = false) or the edges of node[b], which are
+// ---- sampled decoding (HF sample() as the host loop of kvcache.py restates it: mask -> trie -> / temperature -> top-k -> top-p ->
+// softmax -> one draw per row).  Grid B, 1024 threads.  The ITEMS of row b are the ids [0, V) (TRIE = false) or the edges of node[b], which are
 // sorted by token id (TRIE = true, with the bounds handling of decode_pick_trie_kernel); an item is a CANDIDATE when its id passes
 // pick_allowed and its logit is no NaN.
 //   top-k   x_k = the top_k-th largest candidate logit (with multiplicity); every candidate >= x_k is kept (ties at the threshold
 //           included, as `lg < kth` does on the host); top_k == 0 or >= the number of candidates keeps them all.  Logits are bf16, so
 //           x_k is found exactly by a two-pass radix select over the order-preserving 16-bit key: two 256-bin LDS histograms, no sort.
 //   weight  w = exp((x - m) / T) in fp32, m = the largest candidate logit (always kept): the total is >= 1; w(-inf) = 0.
+//   top-p   (HF's TopPLogitsWarper after top-k; top_p >= 1: off, the two passes below are skipped)  a logit value x stays iff the
+//           weight S(x) of the top-k survivors with a STRICTLY larger logit is < top_p * W, W their total; candidates that share a
+//           logit value stay or go together (HF breaks an exact tie at the boundary by sort order), the class of the maximum always
+//           stays (S = 0).  The smallest staying key is found like x_k, by two more passes over the row (high byte, then low byte
+//           inside the boundary bin) whose histograms hold weight MASS instead of counts: floor(w * 2^40) as a 64-bit integer, added
+//           with integer LDS atomics -- integer adds commute, so the masses and with them the boundary do not depend on the order
+//           in which threads arrive (no floating-point atomics anywhere).  V <= 2^23 keeps the total below 2^63; the truncation
+//           loses < V * 2^-40 of a total >= 1.  S and W are compared as (double)S < (double)top_p * (double)W.
 //   draw    u = philox_u01(word 0 of Philox counter rng[1] + cnt*B + b, key rng[0]); the pick is the first kept item whose running sum
 //           of weights, in item order, exceeds u * total -- past the end (rounding): the last kept item with w > 0.  Each thread owns
 //           a contiguous item range and sums it in order; a block scan of the 1024 sums gives every range its start.  The order is
 //           fixed, so equal (logits, rng, cnt) give equal tokens, eager or replayed.
-// The four passes re-read the row (64 KB at V = 32 000: L2-resident right after the lm_head wrote it); the two histogram passes
-// stride over the items, the two summing passes walk each thread's own range.  A row without a kept candidate of non-zero weight
-// emits `eos` and keeps its node.  Nothing outside logits[b, 0..V), the tables and state/out/u_out[cnt*B + b] is touched.
+// The four (top-p: six) passes re-read the row (64 KB at V = 32 000: L2-resident right after the lm_head wrote it); the histogram
+// passes stride over the items, the two summing passes walk each thread's own range.  A row without a kept candidate of non-zero
+// weight emits `eos` and keeps its node.  kept_out (nullable): kept_out[cnt*B + b] = the number of candidates kept by both warpers, 0
+// for such an `eos` row; finished rows write none.  Nothing outside logits[b, 0..V), the tables and state/out/u_out/kept_out[cnt*B + b]
+// is touched.
 constexpr int SAMP_T = 1024;
 // inclusive scan over the SAMP_T threads (in each wave, then over the 16 wave totals in wave order); `total` to every thread
 template <typename T>
@@ -182,15 +192,29 @@ __device__ __forceinline__ void samp_select(const int* hist, int k, int* bin, in
     if (tid < 256 && above < k && above + c >= k) { *bin = 255 - tid; *rank = k - above; }
     __syncthreads();
 }
+// the same for a histogram of weight masses: the bin in which `above0` + the mass counted from the top first reaches top_p * W (W == 0:
+// this histogram's total), and the mass above that bin.  Selects nothing when the histogram is empty.
+__device__ __forceinline__ void samp_select_mass(const unsigned long long* mass, unsigned long long above0, float top_p, unsigned long long W,
+                                                 int* bin, unsigned long long* above, unsigned long long& total) {
+    const int tid = threadIdx.x;
+    const unsigned long long c = tid < 256 ? mass[255 - tid] : 0ull;
+    const unsigned long long upto = above0 + samp_scan<unsigned long long>(c, total);
+    const double lim = (double)top_p * (double)(W ? W : total);
+    if (tid < 256 && c > 0 && (double)(upto - c) < lim && (double)upto >= lim) { *bin = 255 - tid; *above = upto - c; }
+    __syncthreads();
+}
+constexpr float SAMP_MASS_ONE = 1099511627776.f;                      // 2^40: the fixed-point unit of the top-p masses
 template <bool TRIE>
 __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t* __restrict__ logits, int ldl, int V, int special0,
                                                                     int nspecial, const int* __restrict__ toff, const int* __restrict__ ttok,
                                                                     const int* __restrict__ tnxt, int n_nodes, int* __restrict__ node,
-                                                                    float temperature, int top_k, const uint64_t* __restrict__ rng,
-                                                                    float* __restrict__ u_out, int* __restrict__ state, int* __restrict__ out,
-                                                                    int max_steps, int B, int eos, int pad) {
+                                                                    float temperature, int top_k, float top_p,
+                                                                    const uint64_t* __restrict__ rng, float* __restrict__ u_out,
+                                                                    int* __restrict__ kept_out, int* __restrict__ state,
+                                                                    int* __restrict__ out, int max_steps, int B, int eos, int pad) {
     __shared__ int hist[2][256];
-    __shared__ int s_bin[2], s_rank[2], s_max, s_first, s_last;
+    __shared__ unsigned long long mass[2][256], s_above[2];
+    __shared__ int s_bin[2], s_rank[2], s_pbin[2], s_max, s_first, s_last, s_kept;
     __shared__ float s_u;
     const int b = blockIdx.x, tid = threadIdx.x;
     const bf16_t* row = logits + (long)b * ldl;
@@ -201,8 +225,9 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
         philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)rng[0], (uint32_t)(rng[0] >> 32), r);
         s_u = philox_u01(r[0]);
         if (u_out && cnt >= 0 && cnt < max_steps) u_out[(long)cnt * B + b] = s_u;
-        s_max = -1; s_first = PICK_NONE; s_last = -1;
+        s_max = -1; s_first = PICK_NONE; s_last = -1; s_kept = 0;
         s_bin[0] = s_bin[1] = 0; s_rank[0] = s_rank[1] = 0;
+        s_pbin[0] = s_pbin[1] = 0; s_above[0] = s_above[1] = 0;
     }
     if (state[B + b] != 0) {                                          // a finished row emits `pad` whatever it would draw (fin[b] is
         if (tid == 0) pick_emit(state, out, max_steps, B, b, pad, eos, pad);   // written by this block's thread 0 alone)
@@ -264,11 +289,47 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
         const float x = logit_of(k);
         return x == -INFINITY ? 0.f : x == m ? 1.f : expf((x - m) / T);
     };
+    if (top_p < 1.f) {
+        // top-p pass 1: the weight mass of the top-k survivors per high byte
+        if (tid < 256) mass[0][tid] = mass[1][tid] = 0;
+        __syncthreads();
+        auto mass_of = [&](int k) -> unsigned long long { return (unsigned long long)(weight_of(k) * SAMP_MASS_ONE); };
+        for (int i = tid; i < n; i += SAMP_T) {
+            const int k = key_of(i, v);
+            const unsigned long long q = k < 0 ? 0ull : mass_of(k);
+            if (q) atomicAdd(&mass[0][k >> 8], q);
+        }
+        __syncthreads();
+        unsigned long long W, sub;
+        samp_select_mass(mass[0], 0ull, top_p, 0ull, &s_pbin[0], &s_above[0], W);
+        if (W > 0) {                                                  // (W == 0: nothing weighs anything, the row emits `eos`)
+            // top-p pass 2: the same per low byte inside the boundary's high byte
+            const int hb = s_pbin[0];
+            for (int i = tid; i < n; i += SAMP_T) {
+                const int k = key_of(i, v);
+                const unsigned long long q = (k >= 0 && (k >> 8) == hb) ? mass_of(k) : 0ull;
+                if (q) atomicAdd(&mass[1][k & 255], q);
+            }
+            __syncthreads();
+            samp_select_mass(mass[1], s_above[0], top_p, W, &s_pbin[1], &s_above[1], sub);
+            thr = max(thr, (hb << 8) | s_pbin[1]);                    // (the boundary bin holds a top-k survivor: it is >= thr already)
+        }
+    }
     // pass 3: each thread sums the weights of its own contiguous items, in order
     const int per = (n + SAMP_T - 1) / SAMP_T;
     const int i0 = (int)min((long)tid * per, (long)n), i1 = (int)min((long)i0 + per, (long)n);
     float mine = 0.f;
-    for (int i = i0; i < i1; ++i) mine += weight_of(key_of(i, v));
+    int kept = 0;
+    for (int i = i0; i < i1; ++i) {
+        const int k = key_of(i, v);
+        mine += weight_of(k);
+        kept += k >= thr;                                             // (no candidate: k = -1 < thr)
+    }
+    if (kept_out) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
+        if ((tid & 63) == 0) atomicAdd(&s_kept, kept);
+    }
     float total;
     float run = samp_scan<float>(mine, total) - mine;                 // the running sum in front of item i0
     // pass 4: the same sums again, against u * total
@@ -290,6 +351,8 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
         const bool none = i < 0;
         if (!none) key_of(i, v);
         pick_emit(state, out, max_steps, B, b, none ? eos : v, eos, pad);
+        const int cnt = state[7 * B + 2];
+        if (kept_out && cnt >= 0 && cnt < max_steps) kept_out[(long)cnt * B + b] = none ? 0 : s_kept;
         if (TRIE && !none) {
             const int nx = tnxt[e0 + i];
             if (nx >= 0 && nx < n_nodes) node[b] = nx;
@@ -362,22 +425,32 @@ int nv_decode_pick_trie_bf16(const void* logits, int ldl, int V, int special0, i
     return nv_check_launch();
 }
 
-int nv_decode_pick_sample_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
-                               const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, const unsigned long long* rng,
-                               float* u_out, int* state, int* out, int max_steps, int B, int eos, int pad, void* stream) {
+int nv_decode_pick_sample_topp_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                                    const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, float top_p,
+                                    const unsigned long long* rng, float* u_out, int* kept_out, int* state, int* out, int max_steps, int B,
+                                    int eos, int pad, void* stream) {
     if (!logits || !rng || !state || !out || B <= 0 || V <= 0 || ldl < V || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
     if (!(temperature > 0.f && temperature <= 3.402823466e38f) || top_k < 0) return NV_ERR_ARG;      // (a NaN fails both comparisons)
+    if (!(top_p > 0.f && top_p <= 1.f)) return NV_ERR_ARG;                                           // (so does this one)
+    if (top_p < 1.f && V > (1 << 23)) return NV_ERR_ARG;                                             // the 64-bit masses: V * 2^40 < 2^63
     const bool trie = trie_off || trie_tok || trie_nxt || node || n_nodes != 0;
     if (trie && (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0)) return NV_ERR_ARG;
     if (trie)
         NV_LAUNCH(decode_pick_sample_kernel<true>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
-                  nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, (const uint64_t*)rng, u_out, state, out, max_steps,
-                  B, eos, pad);
+                  nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, top_p, (const uint64_t*)rng, u_out, kept_out,
+                  state, out, max_steps, B, eos, pad);
     else
         NV_LAUNCH(decode_pick_sample_kernel<false>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
-                  nspecial, nullptr, nullptr, nullptr, 0, nullptr, temperature, top_k, (const uint64_t*)rng, u_out, state, out, max_steps, B,
-                  eos, pad);
+                  nspecial, nullptr, nullptr, nullptr, 0, nullptr, temperature, top_k, top_p, (const uint64_t*)rng, u_out, kept_out, state,
+                  out, max_steps, B, eos, pad);
     return nv_check_launch();
+}
+
+int nv_decode_pick_sample_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                               const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, const unsigned long long* rng,
+                               float* u_out, int* state, int* out, int max_steps, int B, int eos, int pad, void* stream) {
+    return nv_decode_pick_sample_topp_bf16(logits, ldl, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k,
+                                           1.0f, rng, u_out, nullptr, state, out, max_steps, B, eos, pad, stream);
 }
 
 int nv_decode_advance(int* state, int B, int cap, void* stream) {

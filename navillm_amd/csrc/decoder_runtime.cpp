@@ -19,6 +19,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/navillm_hip.h"
+#include "../../include/navillm_hip_topp.h"
 
 namespace {
 
@@ -319,11 +320,12 @@ int nv_decoder_extend(const nv_decoder* p, const void* x_in, const int* pos, con
 //   state: nv_decode_state_ints(B) ints (tok|fin|len|pos|crow|grow|last|dyn|cnt);  out [max_steps, B] picked tokens
 // nv_decoder_trie_step is the same step with the argmax taken over the children of each sample's trie node (node [B], moved along
 // the picked edge); nv_decoder_sample_step draws the token instead (nv_decode_pick_sample_bf16: temperature, top-k, one Philox draw
-// per row keyed by the device words rng = {seed, offset}), over the vocabulary or over the node's children.  All three are
-// decode_step() below: `node == nullptr` selects the unconstrained candidates, `rng == nullptr` the argmax.
+// per row keyed by the device words rng = {seed, offset}), over the vocabulary or over the node's children, and
+// nv_decoder_sample_topp_step adds the top-p warper (nv_decode_pick_sample_topp_bf16; top_p = 1 is nv_decoder_sample_step).  All four
+// are decode_step() below: `node == nullptr` selects the unconstrained candidates, `rng == nullptr` the argmax.
 static int decode_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                        const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
-                       const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
+                       float top_p, const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
                        void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !hs || !embed || !lm_head || !logits || !x || !state || !out || !kv0 || !attn_buf || !lse || !workspace) return NV_ERR_ARG;
     if (B <= 0 || Vp < V || V <= 0) return NV_ERR_ARG;
@@ -332,8 +334,8 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
     if (B <= 16 && (d & 31) == 0) rc = nv_gemv_bf16(hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, stream);
     else rc = nv_gemm_bf16_ws(0, hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, 0, p->gemm_ws, stream);
     if (rc != NV_OK) return rc;
-    if (rng) rc = nv_decode_pick_sample_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k,
-                                             rng, nullptr, state, out, max_steps, B, eos, pad, stream);
+    if (rng) rc = nv_decode_pick_sample_topp_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature,
+                                                  top_k, top_p, rng, nullptr, nullptr, state, out, max_steps, B, eos, pad, stream);
     else if (node) rc = nv_decode_pick_trie_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out,
                                             max_steps, B, eos, pad, stream);
     else rc = nv_decode_pick_bf16(logits, Vp, V, special0, nspecial, state, out, max_steps, B, eos, pad, stream);
@@ -348,7 +350,7 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
 int nv_decoder_greedy_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B,
                            int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, nullptr, logits, x, state,
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, 1.f, nullptr, logits, x, state,
                        out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
@@ -357,17 +359,27 @@ int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const
                          int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0) return NV_ERR_ARG;
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0.f, 0, nullptr, logits, x,
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0.f, 0, 1.f, nullptr, logits, x,
                        state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+}
+
+int nv_decoder_sample_topp_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
+                                const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature,
+                                int top_k, float top_p, const unsigned long long* rng, void* logits, void* x, int* state, int* out,
+                                int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    if (!rng) return NV_ERR_ARG;                  // (the trie arguments, temperature, top_k and top_p are checked by the pick)
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, top_p,
+                       rng, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
 int nv_decoder_sample_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
                            const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
                            void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!rng) return NV_ERR_ARG;                  // (the trie arguments, temperature and top_k are checked by the pick)
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, rng,
-                       logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return nv_decoder_sample_topp_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature,
+                                       top_k, 1.0f, rng, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace,
+                                       workspace_bytes, stream);
 }
 
 }  // extern "C"

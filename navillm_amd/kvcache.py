@@ -22,6 +22,7 @@ Everything arithmetic is a launch of the same HIP kernels as the training path (
 """
 import ctypes
 import math
+import numbers
 import os
 
 import numpy as np
@@ -72,6 +73,21 @@ def flatten_trie(trie, eos, V, special_ids):
     return np.asarray(off, np.int32), np.asarray(tok, np.int32), np.asarray(nxt, np.int32), eligible
 
 
+def _top_p_warp(lg, top_p):
+    """HF's TopPLogitsWarper (min_tokens_to_keep = 1) on fp32 logits [B, V], by the rule of `decode_pick_sample_kernel`: a logit value
+    stays iff the softmax weight of the STRICTLY larger logits is < top_p; equal logits stay or go together (HF breaks an exact tie
+    at the boundary by sort order); the maximum stays.  -> the logits with what goes at -inf"""
+    xs, order = torch.sort(lg, dim=-1, descending=True)
+    p = torch.softmax(xs, dim=-1)
+    before = torch.cumsum(p, dim=-1) - p                                # the weight sorted in front of each entry ...
+    first = torch.ones_like(xs, dtype=torch.bool)
+    first[:, 1:] = xs[:, 1:] != xs[:, :-1]                              # ... which at the first entry of a run of equal logits is the
+    above = torch.cummax(torch.where(first, before, torch.zeros_like(before)), dim=-1).values       # weight strictly above the run
+    drop = above >= top_p
+    drop[:, 0] = False
+    return lg.masked_fill(torch.zeros_like(drop).scatter(1, order, drop), float("-inf"))
+
+
 class KVCacheLM:
     def __init__(self, model, batch_size, capacity=1024):
         cfg = model.cfg
@@ -87,7 +103,7 @@ class KVCacheLM:
         self._greedy = None                                    # device-side decode loop: buffers + captured hipGraphs
         self._trie_host, self._trie_dev = None, None           # the flattened trie of the last constrained call, host and device
         self.last_generate = None                              # {"loop": "device" | "host", "trie": bool} of the last generate()
-        self.last_sample = None                                # {"seed", "offset", "temperature", "top_k"} of a device-sampled generate()
+        self.last_sample = None                                # {"seed", "offset", "temperature", "top_k"} of a device-sampled generate(), + "top_p" when < 1
         self._key_ids = {}                                     # reuse key (hashable) -> small int
         self.reset()
 
@@ -254,18 +270,28 @@ class KVCacheLM:
 
     @torch.no_grad()
     def generate(self, ids_list, vis_idx_list=None, vis_all=None, max_new_tokens=50, eos_token_id=2, pad_token_id=0,
-                 trie=None, do_sample=False, temperature=1.0, top_k=50):
+                 trie=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0):
         """Greedy decoding with HF's bookkeeping (`generate(do_sample=False)`): finished rows emit `pad_token_id`, the
         loop ends when every row has produced `eos_token_id` or after `max_new_tokens`.  `trie` (tools/trie.py protocol:
         `.root`, `.get_child_index(node)`, `.get_next_node(node, w)`) constrains each step like TrieLogitsProcessor.
         do_sample=True (tasks/agents/llava.py:58-62 forwards `--do_sample --temperature`): HF's `sample()` -- after the mask and
-        the trie, logits / temperature, the default top-k (50) warper, softmax, one multinomial draw per row from torch's CUDA
-        generator (same distribution as the reference; the streams of two RNG implementations cannot be compared draw by draw).
+        the trie, logits / temperature, the default top-k (50) warper, the top-p warper, softmax, one multinomial draw per row from
+        torch's CUDA generator (same distribution as the reference; the streams of two RNG implementations cannot be compared draw by
+        draw).  top_p (None or 1.0: off; else a real number in (0, 1), anything else raises ValueError): HF's TopPLogitsWarper -- with W
+        the total softmax weight of the top-k survivors, a logit value stays iff the weight of the survivors with a strictly larger
+        logit is < top_p * W; equal logits stay or go together (HF breaks an exact tie at the boundary by sort order), the maximum
+        always stays.  do_sample=False ignores it, as HF does.
         With NAVILLM_DEVICE_SAMPLE=1 a sampled call runs the device loop too (temperature finite and > 0, top_k None or an int >= 0,
         room in the cache, an eligible trie; anything else keeps the host loop): the same distribution, drawn by
         `decode_pick_sample_kernel` from Philox counters taken from torch's CUDA generator (`torch.manual_seed` makes a run
-        reproducible); `last_sample` then records the seed, the offset and the two settings.
+        reproducible); `last_sample` then records the seed, the offset, temperature and top_k, and top_p when the warper is on.
         Returns B lists with the new tokens only."""
+        if do_sample:                                              # (checked before any work, whichever loop will run)
+            if top_p is None:
+                top_p = 1.0
+            if isinstance(top_p, bool) or not isinstance(top_p, numbers.Real) or not 0.0 < top_p <= 1.0:       # (a NaN fails the comparison)
+                raise ValueError(f"KVCacheLM.generate: top_p must be None, 1.0 or a real number in (0, 1), not {top_p!r}")
+            top_p = float(top_p)
         B = self.B
         self.reset()
         seqs = [list(x) for x in ids_list]
@@ -287,8 +313,8 @@ class KVCacheLM:
                 if do_sample:                                      # one Philox counter per draw, accounted like the attention-probability dropout
                     seed, offset = _fn._philox_take(self.model.device, 4 * B * max_new_tokens)
                     sampler = {"seed": int(seed), "offset": int(offset), "temperature": float(temperature),
-                               "top_k": min(int(top_k or 0), 2 ** 31 - 1)}
-                    self.last_sample = dict(sampler)
+                               "top_k": min(int(top_k or 0), 2 ** 31 - 1), "top_p": top_p}
+                    self.last_sample = {k: v for k, v in sampler.items() if k != "top_p" or top_p < 1.0}
                 return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables, sampler)
         out = [[] for _ in range(B)]
         unfinished = [True] * B
@@ -309,6 +335,8 @@ class KVCacheLM:
                 if top_k and top_k < lg.shape[-1]:
                     kth = torch.topk(lg, top_k, dim=-1).values[:, -1:]
                     lg = lg.masked_fill(lg < kth, float("-inf"))
+                if top_p < 1.0:
+                    lg = _top_p_warp(lg, top_p)
                 nxt = torch.multinomial(torch.softmax(lg, dim=-1), 1).view(-1).tolist()
             else:
                 nxt = torch.argmax(lg, dim=-1).tolist()
@@ -371,7 +399,7 @@ class KVCacheLM:
     def _greedy_step(self, g, eos, pad, stream, dec, trie=None, sampler=None):
         """`dec`: the native decoder, resolved by the caller BEFORE any stream capture (nothing here may allocate or rebuild);
         `trie`: the device tables of `_trie_tables` -> the step picks among the children of g["node"];
-        `sampler`: temperature and top_k -> the step draws its token, keyed by the two words in g["rng"]"""
+        `sampler`: temperature, top_k and top_p -> the step draws its token, keyed by the two words in g["rng"]"""
         m, cfg, st = self.model, self.model.cfg, self.model.store
         sp = cfg.special_token_ids
         head = (dec, g["hs"].data_ptr(), st.p("lang_model.model.embed_tokens.weight").data_ptr(), st.lm_head_padded().data_ptr(), st.vocab_pad,
@@ -381,8 +409,14 @@ class KVCacheLM:
         tr = (None, None, None, 0, None) if trie is None else (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(),
                                                                trie["n_nodes"], g["node"].data_ptr())
         if sampler is not None:
-            _lib.check(ops._L().nv_decoder_sample_step(*head, *tr, sampler["temperature"], sampler["top_k"], g["rng"].data_ptr(), *tail),
-                       "nv_decoder_sample_step")
+            # what the kernel is handed is an fp32: a top_p that rounds to 1 is off, one that rounds to 0 keeps the maximum alone either way
+            p32 = max(float(np.float32(sampler["top_p"])), float(np.finfo(np.float32).tiny))
+            if p32 < 1.0:
+                _lib.check(ops._L().nv_decoder_sample_topp_step(*head, *tr, sampler["temperature"], sampler["top_k"], p32, g["rng"].data_ptr(),
+                                                                *tail), "nv_decoder_sample_topp_step")
+            else:
+                _lib.check(ops._L().nv_decoder_sample_step(*head, *tr, sampler["temperature"], sampler["top_k"], g["rng"].data_ptr(), *tail),
+                           "nv_decoder_sample_step")
         elif trie is None:
             _lib.check(ops._L().nv_decoder_greedy_step(*head, *tail), "nv_decoder_greedy_step")
         else:
@@ -393,7 +427,7 @@ class KVCacheLM:
         """prefill through `extend` (host-built indices, once), then max_new_tokens replays of ONE captured step
         (nv_decoder_greedy_step: lm_head -> masked argmax + finished/pad bookkeeping -> cache indices -> embedding -> decoder layers;
         with `trie`, the device tables of `_trie_tables`: nv_decoder_trie_step, the argmax over the children of each row's trie node;
-        with `sampler`: nv_decoder_sample_step, a draw among the same candidates).
+        with `sampler`: nv_decoder_sample_step / nv_decoder_sample_topp_step, a draw among the same candidates).
         The host never waits for a token: it polls the `fin` flags two steps behind and trims the output where HF would have stopped."""
         B, dev = self.B, self.model.device
         g = self._greedy_state(max_new_tokens)
@@ -423,8 +457,8 @@ class KVCacheLM:
         if trie is not None:                                   # the tables' addresses and the node count are frozen launch arguments too
             g["node"].zero_()                                  # every row starts at the root
             key += (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(), trie["n_nodes"], g["node"].data_ptr())
-        if sampler is not None:                                # so are the two settings; the seed and the offset travel through g["rng"]
-            key += (sampler["temperature"], sampler["top_k"], g["rng"].data_ptr())
+        if sampler is not None:                                # so are the three settings; the seed and the offset travel through g["rng"]
+            key += (sampler["temperature"], sampler["top_k"], sampler["top_p"], g["rng"].data_ptr())
             words = np.array([sampler["seed"], sampler["offset"]], dtype=np.uint64).view(np.int64)
             g["rng"].copy_(ops.h2d(torch.from_numpy(words), dev))
         if USE_HIP_GRAPH and g["graphs"].get(kind, (None, None))[0] != key:

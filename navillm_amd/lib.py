@@ -1,7 +1,7 @@
 """ctypes binding of libnavillm_hip.so -- the ONLY way the package reaches the GPU kernels.
 
-There is no fallback: if the library is missing or a symbol declared in include/navillm_hip.h is
-not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
+There is no fallback: if the library is missing or a symbol declared in include/navillm_hip.h or
+include/navillm_hip_topp.h is not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
 never imported from here.)
 """
 import ctypes as C
@@ -140,6 +140,13 @@ SIGNATURES = {
     "nv_comm_destroy": (i, [vp]),
 }
 
+# the same for include/navillm_hip_topp.h (the top-p entry points; a table of its own because the suite pins the size of the one above)
+TOPP_SIGNATURES = {
+    "nv_decode_pick_sample_topp_bf16": (i, [vp, i, i, i, i, ip, ip, ip, i, ip, f, i, f, vp, fp, ip, ip, ip, i, i, i, i, vp]),
+    "nv_decoder_sample_topp_step": (i, [vp, vp, vp, vp, i, i, i, i, ip, ip, ip, i, ip, f, i, f, vp, vp, vp, ip, ip, i, ip, vp, fp, i, i, i, i, vp,
+                                        sz, vp]),
+}
+
 _lib = None
 
 
@@ -162,7 +169,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m navillm_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **TOPP_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -4,9 +4,10 @@ prompt, then N single-token steps through the K/V cache -- host loop (token choi
 --trie[=WORDS,DEPTH] (default 2000,24): the same three loops under a trie constraint -- WORDS random words of DEPTH tokens each, about
 half of them branching off an earlier word, so every row decodes DEPTH tokens and then eos.  --reps=R timed calls per loop (default 2;
 the last one is reported, with the spread over all but the first); --free with --trie: the unconstrained loops as well.
---sample [--temperature=T --top-k=K] (defaults 0.01 and 50: the reference's evaluation scripts run --do_sample --temperature 0.01):
-generate(do_sample=True) instead, host loop (torch topk / softmax / multinomial per token) vs the device loop of NAVILLM_DEVICE_SAMPLE;
-combines with --trie, --small and --free."""
+--sample [--temperature=T --top-k=K --top-p=P] (defaults 0.01, 50 and none: the reference's evaluation scripts run --do_sample
+--temperature 0.01): generate(do_sample=True) instead, host loop (torch topk / softmax / multinomial per token) vs the device loop of
+NAVILLM_DEVICE_SAMPLE; --top-p adds the nucleus warper to both (without it the call carries no top_p at all); combines with --trie,
+--small and --free."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from navillm_amd import config as nvcfg
@@ -66,6 +67,8 @@ ids = [[1] + torch.randint(3, cfg.base_vocab_size, (L - 1 + b,), generator=g).to
 sample = None
 if "--sample" in sys.argv:
     sample = dict(do_sample=True, temperature=float(opt("temperature", 0.01)), top_k=int(opt("top-k", 50)))
+    if opt("top-p", None) is not None:
+        sample["top_p"] = float(opt("top-p", None))
 trie, eos = None, -1
 if any(a == "--trie" or a.startswith("--trie=") for a in sys.argv):
     n_words, depth = (int(x) for x in opt("trie", "2000,24").split(","))
