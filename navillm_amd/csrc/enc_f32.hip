@@ -574,7 +574,10 @@ int nv_gemm_f32_ws(int layout, const float* A, const float* B, float* C, const f
                          (a_kc ? !(K & 3) : !(M & 3)) && (b_kc ? !(K & 3) : !(N & 3));
     if (aligned) {
         const long a_rows = a_kc ? M : K, a_cols = a_kc ? K : M, b_rows = b_kc ? N : K, b_cols = b_kc ? K : N;
-        const uint32_t ab = (uint32_t)(((a_rows - 1) * (long)lda + a_cols) * 4), bb = (uint32_t)(((b_rows - 1) * (long)ldb + b_cols) * 4);
+        // K == 0: an operand has no rows (or no columns) and (rows - 1) * ld + cols would be negative (a 4 GiB window after the cast)
+        // or span rows that need not exist, while the kernel still issues its first tile load: a zero-byte window reads nothing
+        const uint32_t ab = K ? (uint32_t)(((a_rows - 1) * (long)lda + a_cols) * 4) : 0u;
+        const uint32_t bb = K ? (uint32_t)(((b_rows - 1) * (long)ldb + b_cols) * 4) : 0u;
         hipStream_t st = (hipStream_t)stream;
         dim3 g3 = grid;
         const int blocks = grid.x * grid.y, ktiles = (K + FBK - 1) / FBK;
