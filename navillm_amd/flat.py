@@ -76,6 +76,7 @@ class FlatStore:
         self.grad = {g: torch.zeros(tot[g], dtype=dt[g], device=self.device) for g in tot}
         self.exp_avg = None
         self.exp_avg_sq = None
+        self.master = None        # {"lm": fp32 master weights} under FlatAdamW(state_precision="fp32_master"), else None
         self._upd = None          # an AdamW update of the LM group still running on the optimizer's side stream (FlatAdamW.step, round 6)
 
     # ---- asynchronous update of the LM group (navillm_amd/optim.py::FlatAdamW.step with overlap): the update kernels run on a side stream,
@@ -228,7 +229,7 @@ class FlatStore:
         self.names["lm"] = keep
         self.total["lm"] = off
         self.grad = None
-        self.exp_avg = self.exp_avg_sq = None
+        self.exp_avg = self.exp_avg_sq = self.master = None
         for n, p in named_params.items():
             p.grad = None
             p.requires_grad_(False)
@@ -237,15 +238,27 @@ class FlatStore:
     def release_grads(self, named_params):
         """inference deployment that keeps the parameters: drop the gradient buffers and the optimizer state only"""
         self.grad = None
-        self.exp_avg = self.exp_avg_sq = None
+        self.exp_avg = self.exp_avg_sq = self.master = None
         for p in named_params.values():
             p.grad = None
             p.requires_grad_(False)
 
-    def init_optimizer_state(self):
+    def init_optimizer_state(self, precision="bf16"):
+        """moments in the parameters' own dtype ("bf16", "stochastic": what torch.optim.AdamW keeps for them); "fp32_master": the LM
+        group's moments in fp32 plus a zero fp32 master buffer, which adopts the weights at the first step (the kernel's self-healing
+        rule, include/navillm_hip_optim.h).  Existing state of another precision is converted (bf16 -> fp32 exact, fp32 -> bf16 RNE)."""
+        dt = {g: (torch.float32 if precision == "fp32_master" else t.dtype) for g, t in self.param.items()}
         if self.exp_avg is None:
-            self.exp_avg = {g: torch.zeros_like(t) for g, t in self.param.items()}
-            self.exp_avg_sq = {g: torch.zeros_like(t) for g, t in self.param.items()}
+            self.exp_avg = {g: torch.zeros_like(t, dtype=dt[g]) for g, t in self.param.items()}
+            self.exp_avg_sq = {g: torch.zeros_like(t, dtype=dt[g]) for g, t in self.param.items()}
+        for buf in (self.exp_avg, self.exp_avg_sq):
+            for g in buf:
+                if buf[g].dtype != dt[g]:
+                    buf[g] = buf[g].to(dt[g])
+        if precision != "fp32_master":
+            self.master = None
+        elif self.master is None or self.master["lm"].numel() != self.param["lm"].numel():
+            self.master = {"lm": torch.zeros_like(self.param["lm"], dtype=torch.float32)}
 
     def load_state_dict_tensors(self, sd):
         self.wait_params()

@@ -1,7 +1,7 @@
 """ctypes binding of libnavillm_hip.so -- the ONLY way the package reaches the GPU kernels.
 
 There is no fallback: if the library is missing or a symbol declared in include/navillm_hip.h or
-include/navillm_hip_topp.h is not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
+include/navillm_hip_topp.h / include/navillm_hip_optim.h is not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
 never imported from here.)
 """
 import ctypes as C
@@ -147,6 +147,13 @@ TOPP_SIGNATURES = {
                                         sz, vp]),
 }
 
+# the same for include/navillm_hip_optim.h (AdamW with fp32 master weights / stochastic rounding)
+_d, _ull = C.c_double, C.c_ulonglong
+OPTIM_SIGNATURES = {
+    "nv_adamw_master": (i, [vp, vp, fp, fp, fp, l, _d, _d, _d, _d, _d, i, fp, i, vp]),
+    "nv_adamw_sr": (i, [vp, vp, vp, vp, l, l, _ull, _d, _d, _d, _d, _d, i, fp, i, vp]),
+}
+
 _lib = None
 
 
@@ -169,7 +176,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m navillm_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TOPP_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TOPP_SIGNATURES, **OPTIM_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -450,6 +450,24 @@ def adamw_(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, clip
                              beta1, beta2, eps, wd, step, _p(clip), _st()), "nv_adamw")
 
 
+def adamw_master_(p, g, master, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, clip=None, zero_grad=False):
+    """AdamW on fp32 master weights and fp32 moments; p (bf16) = RNE(master).  Where p no longer is the rounding of its master the kernel
+    takes p as the master first (include/navillm_hip_optim.h)."""
+    assert p.dtype == BF16 and g.dtype == BF16 and master.dtype == F32 and m.dtype == F32 and v.dtype == F32
+    assert g.numel() == master.numel() == m.numel() == v.numel() == p.numel()
+    _lib.check(_L().nv_adamw_master(p.data_ptr(), g.data_ptr(), master.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), lr, beta1, beta2, eps,
+                                    wd, step, _p(clip), 1 if zero_grad else 0, _st()), "nv_adamw_master")
+
+
+def adamw_sr_(p, g, m, v, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, clip=None, zero_grad=False, elem0=0, seed=0):
+    """AdamW in fp32 registers on bf16 parameter and moments, the three stores stochastically rounded; the random bits are a function of
+    (seed, step, elem0 + index, array) alone (include/navillm_hip_optim.h)."""
+    assert p.dtype == BF16 and g.dtype == BF16 and m.dtype == BF16 and v.dtype == BF16
+    assert g.numel() == m.numel() == v.numel() == p.numel()
+    _lib.check(_L().nv_adamw_sr(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), elem0, seed, lr, beta1, beta2, eps, wd, step,
+                                _p(clip), 1 if zero_grad else 0, _st()), "nv_adamw_sr")
+
+
 # ------------------------------------------------------------------ fp32 encoder ops
 def gemm_f32(layout, A, B, bias=None, out=None, accumulate=False):
     _chk2d(A, F32)

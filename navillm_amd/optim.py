@@ -20,7 +20,14 @@ its own step count.
 Optimizer state lives in this flat layout; `load_state_dict` also accepts the reference checkpoint's `optimizer` entry
 (`torch.optim.AdamW.state_dict()` as written by tools/optims.py:65-78 and read back at :26-29) and `reference_state_dict()`
 writes one, so a run can be resumed on either side (the conversion is `reference_optimizer_to_flat` /
-`flat_to_reference_optimizer` below; pinned by tests/golden/g13_optimizer_bf16.npz)."""
+`flat_to_reference_optimizer` below; pinned by tests/golden/g13_optimizer_bf16.npz).
+
+State precision of the bf16 LM group (`state_precision=` / NAVILLM_ADAMW_STATE; DESIGN.md "AdamW state precision"): "bf16" is the
+reference-exact default above.  At the reference's lr = 1e-5 it leaves most weights frozen (an update of ~lr is below half a bf16
+spacing of every weight larger than ~0.005, and `v * 0.999` rounds back to `v`), so two opt-in modes compute the update in fp32
+registers (csrc/adamw_hp.hip): "fp32_master" keeps an fp32 master copy and fp32 moments and writes p = RNE_bf16(master); "stochastic"
+keeps bf16 state and rounds the three stores stochastically with Philox bits keyed by (`sr_seed`, step, element index), the same on every
+data-parallel rank.  The fp32 group is the same in all three modes, and so is an fp32 LM (it already has fp32 parameters and moments)."""
 import os
 
 import torch
@@ -73,7 +80,8 @@ def reference_optimizer_to_flat(store, sd, names=None):
     if order is None:
         raise ValueError(f"reference optimizer state: {len(idx)} parameters whose shapes fit none of the known parameter orders "
                          f"({[len(c) for c in cands]} names); pass names=names_from_model_state_dict(ckpt['model_state_dict'], cfg)")
-    store.init_optimizer_state()
+    if store.exp_avg is None:
+        store.init_optimizer_state()
     for buf in (store.exp_avg, store.exp_avg_sq):        # an optimizer that has already stepped: no stale moments for parameters the
         for t in buf.values():                           # checkpoint has no entry for
             t.zero_()
@@ -86,7 +94,7 @@ def reference_optimizer_to_flat(store, sd, names=None):
         steps[n] = _step_number(st["step"])
         for buf, key in ((store.exp_avg, "exp_avg"), (store.exp_avg_sq, "exp_avg_sq")):
             v = store._view(buf, n)
-            v.copy_(st[key].to(device=v.device, dtype=v.dtype))
+            v.copy_(st[key].to(device=v.device, dtype=v.dtype))      # (fp32 moments under "fp32_master": the upcast is exact)
     step_count = max(steps.values(), default=0)
     born = {n: step_count - s for n, s in steps.items()}
     g = sd["param_groups"][0]
@@ -103,9 +111,10 @@ def flat_to_reference_optimizer(store, step_count, born, group, names=None):
     for j, n in enumerate(order):
         if n not in born:
             continue
-        state[j] = {"step": torch.tensor(float(step_count - born[n])),
-                    "exp_avg": store._view(store.exp_avg, n).detach().clone().cpu(),
-                    "exp_avg_sq": store._view(store.exp_avg_sq, n).detach().clone().cpu()}
+        dt = store._view(store.param, n).dtype            # the reference keeps a parameter's moments in the parameter's dtype: fp32 LM
+        state[j] = {"step": torch.tensor(float(step_count - born[n])),                 # moments ("fp32_master") are rounded RNE
+                    "exp_avg": store._view(store.exp_avg, n).detach().to(dt, copy=True).cpu(),
+                    "exp_avg_sq": store._view(store.exp_avg_sq, n).detach().to(dt, copy=True).cpu()}
     g = {k: v for k, v in group.items() if k != "params"}
     g.setdefault("amsgrad", False)
     g["params"] = list(range(len(order)))
@@ -131,8 +140,17 @@ def active_segments(store, born):
     return out
 
 
+STATE_PRECISIONS = ("bf16", "fp32_master", "stochastic")
+
+
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=40.0):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=40.0, state_precision=None, sr_seed=0):
+        if state_precision is None:                      # an explicit argument wins over the environment
+            state_precision = os.environ.get("NAVILLM_ADAMW_STATE", "bf16")
+        if state_precision not in STATE_PRECISIONS:
+            raise ValueError(f"FlatAdamW: state_precision {state_precision!r} (argument or NAVILLM_ADAMW_STATE): expected one of {STATE_PRECISIONS}")
+        self.state_precision = state_precision
+        self.sr_seed = int(sr_seed)                      # "stochastic": the Philox key; NOT torch's generator, so every DP rank rounds alike
         self.model = model
         self.store = model.store
         super().__init__([{"params": list(model.parameters())}], dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -140,7 +158,9 @@ class FlatAdamW(torch.optim.Optimizer):
         self.step_count = 0
         self.born = {}                   # parameter name -> number of optimizer steps taken before its first gradient
         self._segs, self._segs_key = None, None
-        self.store.init_optimizer_state()
+        # the modes concern the bf16 LM group; an fp32 LM already has fp32 parameters and moments
+        self._lm_mode = state_precision if self.store.lm_dtype == torch.bfloat16 else "bf16"
+        self.store.init_optimizer_state(self._lm_mode)
         self._clip = torch.ones(2, dtype=torch.float32, device=self.store.device)
         self._clip_valid = False
         # round 4: `optimizer.zero_grad()` (train.py:89) folded into the update kernel -- the gradient is zeroed as it is consumed, the
@@ -217,9 +237,18 @@ class FlatAdamW(torch.optim.Optimizer):
         lr, (b1, b2), eps, wd = g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"]
         clip = self._clip if self._clip_valid else None
 
+        mode = self._lm_mode
+
         def upd(grp, s, e, born):
-            ops.adamw_(st.param[grp][s:e], st.grad[grp][s:e], st.exp_avg[grp][s:e], st.exp_avg_sq[grp][s:e],
-                       self.step_count - born, lr, b1, b2, eps, wd, clip=clip, zero_grad=self.fused_zero_grad)
+            a = (st.param[grp][s:e], st.grad[grp][s:e])
+            k = dict(clip=clip, zero_grad=self.fused_zero_grad)
+            h = (self.step_count - born, lr, b1, b2, eps, wd)
+            if grp != "lm" or mode == "bf16":
+                ops.adamw_(*a, st.exp_avg[grp][s:e], st.exp_avg_sq[grp][s:e], *h, **k)
+            elif mode == "fp32_master":
+                ops.adamw_master_(*a, st.master[grp][s:e], st.exp_avg[grp][s:e], st.exp_avg_sq[grp][s:e], *h, **k)
+            else:                                        # elem0 = the segment's offset: the same bits however the buffer is cut
+                ops.adamw_sr_(*a, st.exp_avg[grp][s:e], st.exp_avg_sq[grp][s:e], *h, elem0=s, seed=self.sr_seed, **k)
         if self.overlap_update and st.grad["lm"].is_cuda:
             # fp32 group (scene encoder, fusion: the very next launches read it) on the launch stream; the LM group on the side stream, cut
             # at the decoder layers' boundaries (the kernel is elementwise: the same values whatever the cut) with an event per layer
@@ -275,12 +304,17 @@ class FlatAdamW(torch.optim.Optimizer):
         self.store.layers_zero = True          # every element is zero now: step() zeroed the updated segments, the gaps were filled here
 
     def state_dict(self):
-        """flat-layout state (copies); not a torch.optim.AdamW state dict"""
+        """flat-layout state (copies); not a torch.optim.AdamW state dict.  "fp32_master" adds the master buffer: a resumed run then
+        continues bit for bit (without it the master restarts from the bf16 parameter, the self-healing rule)."""
         self.store.wait_params()
-        return {"step": self.step_count, "born": dict(self.born),
-                "exp_avg": {g: t.clone() for g, t in self.store.exp_avg.items()},
-                "exp_avg_sq": {g: t.clone() for g, t in self.store.exp_avg_sq.items()},
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        sd = {"step": self.step_count, "born": dict(self.born),
+              "exp_avg": {g: t.clone() for g, t in self.store.exp_avg.items()},
+              "exp_avg_sq": {g: t.clone() for g, t in self.store.exp_avg_sq.items()},
+              "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+              "state_precision": self.state_precision, "sr_seed": self.sr_seed}
+        if self.store.master is not None:
+            sd["master"] = {g: t.clone() for g, t in self.store.master.items()}
+        return sd
 
     def reference_state_dict(self, names=None):
         """this optimizer's state as the reference's `optimizer.state_dict()` (per-parameter, indexed in `names` order; default
@@ -289,7 +323,14 @@ class FlatAdamW(torch.optim.Optimizer):
         return flat_to_reference_optimizer(self.store, self.step_count, self.born, self.param_groups[0], names)
 
     def load_state_dict(self, sd, names=None):
+        """A FlatAdamW state of ANY state precision, or the reference's torch.optim.AdamW entry.  This optimizer keeps its own
+        `state_precision`; moments are cast to its buffers: bf16 -> fp32 is exact, fp32 -> bf16 rounds to nearest even (a state saved
+        under "fp32_master" loses its sub-bf16 bits in a "bf16" / "stochastic" optimizer).  A saved master is taken only by an
+        "fp32_master" optimizer; a missing one is zeroed, so that every element re-adopts its bf16 parameter at the next step.
+        `sr_seed` is restored when the state carries one: a resumed "stochastic" run continues the same stream."""
         self.store.wait_params()
+        if self.store.master is not None and "master" not in sd:
+            self.store.master["lm"].zero_()
         if "state" in sd and "param_groups" in sd and "exp_avg" not in sd:
             # a reference checkpoint's `optimizer` entry (tools/optims.py:26-29 calls exactly this method with it)
             self.step_count, self.born, hyper = reference_optimizer_to_flat(self.store, sd, names)
@@ -307,6 +348,10 @@ class FlatAdamW(torch.optim.Optimizer):
         for g in ("lm", "f32"):
             self.store.exp_avg[g].copy_(sd["exp_avg"][g])
             self.store.exp_avg_sq[g].copy_(sd["exp_avg_sq"][g])
+        if self.store.master is not None and "master" in sd:
+            self.store.master["lm"].copy_(sd["master"]["lm"])
+        if "sr_seed" in sd:
+            self.sr_seed = int(sd["sr_seed"])
         for g, saved in zip(self.param_groups, sd.get("param_groups", [])):
             g.update({k: v for k, v in saved.items() if k != "params"})
 
