@@ -54,6 +54,7 @@ import numpy as np
 import torch
 
 from . import debug
+from . import layer
 from . import ops
 
 BF16, F32, I32 = torch.bfloat16, torch.float32, torch.int32
@@ -119,7 +120,6 @@ class PrefixEpisode:
         self.kv0 = torch.zeros((batch_size,), dtype=I32, device=dev)
         self.prefix = None
         self._slab = {}
-        self._wcache = {}
         self.stats = {"prefix_rows": 0, "suffix_rows": []}
         mode = os.environ.get("NAVILLM_EPISODE_DEFER", "all")
         if os.environ.get("NAVILLM_EPISODE_DEFER_WGRAD", "1") == "0":
@@ -282,23 +282,27 @@ class PrefixEpisode:
         cached = torch.cuda.memory_reserved(self.m.device) - torch.cuda.memory_allocated(self.m.device)
         return self._row_bytes() * cap - held + one_layer + scratch + reserve <= free + cached // 2
 
-    def _weights(self, i):
-        """(Wqkv, Wo, Wgu, Wd, w1, w2, their six gradient views) of layer i: views of the flat store, built once"""
-        st = self.m.store
-        if st._upd is not None:
-            st.wait_params(layer=i)            # (an optimizer update of this layer still on the side stream: FlatAdamW.step, round 6)
-        w = self._wcache.get(i)
-        if w is None:
-            w = self._wcache[i] = self._weights_uncached(i)
-        return w
+    _DST = {"n1": (1, 0), "qkv": (3, 0), "attn": (1, 0), "x1": (1, 0), "n2": (1, 0), "gu": (0, 2), "h": (0, 1), "x2": (1, 0)}
+    _DST32 = {"rstd1": "r1", "rstd2": "r2"}
 
-    def _weights_uncached(self, i):
-        m, st = self.m, self.m.store
-        p = f"lang_model.model.layers.{i}."
-        return (st.qkv(i), st.p(p + "self_attn.o_proj.weight"), st.gate_up(i), st.p(p + "mlp.down_proj.weight"),
-                st.p(p + "input_layernorm.weight"), st.p(p + "post_attention_layernorm.weight"),
-                st.qkv(i, grad=True), st.g(p + "self_attn.o_proj.weight"), st.gate_up(i, grad=True), st.g(p + "mlp.down_proj.weight"),
-                st.g(p + "input_layernorm.weight"), st.g(p + "post_attention_layernorm.weight"))
+    def _dst(self, tag, i, rows, names, E, allm):
+        """where layer i's forward results `names` go for the token rows `rows` (the `dst` mapping of navillm_amd/layer.py): this block
+        of the episode buffers where finish() reads them again (E: the layer's buffers or None; allm: mode "all" keeps everything),
+        otherwise the grow-only scratch `<tag><i>.<name>`, so that rows of varying number do not churn the allocator"""
+        cfg = self.m.cfg
+        n, out = rows.stop - rows.start, {}
+        for name in names:
+            r = self._DST32.get(name)
+            if E is not None and name in E:
+                out[name] = E[name][rows]
+            elif r is not None:
+                out[name] = self._E32[i][r][rows] if allm else self._buf(f"{tag}{i}.{r}", (n,), F32)
+            elif allm and name == "x2" and i + 1 < cfg.num_layers:
+                out[name] = self._E[i + 1]["x"][rows]      # a layer's output IS the next layer's saved input
+            else:
+                cd, cf = self._DST[name]
+                out[name] = self._buf(f"{tag}{i}.{name}", (n, cd * cfg.hidden_size + cf * cfg.intermediate_size))
+        return out
 
     def has_pending_gradients(self):
         """an open episode whose steps ran a backward(): in the deferred forms those gradients exist only here until finish()"""
@@ -523,22 +527,15 @@ class PrefixEpisode:
         layers = []
         x = ops.embed_vis(st.p("lang_model.model.embed_tokens.weight"), ids_d, vix, None,
                           out=self._E[0]["x"][:Mp] if allm else self._buf("pE", (Mp, d)))
+        rows = slice(0, Mp)
         for i in range(L):
-            Wqkv, Wo, Wgu, Wd, w1, w2 = self._weights(i)[:6]
+            lw = st.layer(i)
             # kept until finish(): grow-only slabs, so prefixes of varying length do not churn the allocator; the four Linear
             # inputs live in the episode buffers when the weight gradients are deferred (rows [0, Mp))
             E = self._E[i] if defer else None
-
-            def t(name, width, dt=BF16, E=E, i=i):
-                if E is not None and name in E:
-                    return E[name][:Mp]
-                if allm and name in ("r1", "r2"):
-                    return self._E32[i][name][:Mp]
-                if allm and name == "x2" and i + 1 < L:
-                    return self._E[i + 1]["x"][:Mp]        # a layer's output IS the next layer's saved input
-                return self._buf(f"p{i}.{name}", (Mp, width) if width else (Mp,), dt)
-            n1, rstd1 = ops.rmsnorm_fwd(x, w1, eps, out=t("n1", d), rstd=t("r1", 0, F32))
-            qkv = ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, Lmax, H, hd, out=t("qkv", 3 * d), pos_i32=pos_d)
+            dst = self._dst("p", i, rows, ("n1", "rstd1", "qkv"), E, allm)
+            n1, rstd1 = ops.rmsnorm_fwd(x, lw.w1, eps, out=dst["n1"], rstd=dst["rstd1"])
+            qkv = ops.qkv_rope(n1, lw.Wqkv, m.rope_cos, m.rope_sin, Lmax, H, hd, out=dst["qkv"], pos_i32=pos_d)
             if to_cache:
                 ops.scatter_rows_bf16_(qkv, crow_d, self.cache[i])
             if i == L - 1 and os.environ.get("NAVILLM_EPISODE_PRUNE_TOP", "1") != "0":
@@ -547,14 +544,11 @@ class PrefixEpisode:
                 # always skipped them (`lo = Mp`)
                 layers.append(dict(x=x, n1=n1, rstd1=rstd1, qkv=qkv, attn=None, lse=None, x1=None, n2=None, rstd2=None, gu=None, h=None))
                 break
-            attn = t("attn", d)
+            dst = self._dst("p", i, rows, ("attn", "x1", "n2", "rstd2", "gu", "h", "x2"), E, allm)
+            attn = dst["attn"]
             lse = self._buf(f"p{i}.lse", (B, H, Lmax), F32)
             ops.attn_fwd_varlen(qkv, cu_d, zero_pos0, B, Lmax, H, hd, out=attn, lse2=lse)
-            x1 = ops.gemm_bf16(ops.NT, attn, Wo, out=t("x1", d), R=x, epilogue=ops.EPI_RESID)
-            n2, rstd2 = ops.rmsnorm_fwd(x1, w2, eps, out=t("n2", d), rstd=t("r2", 0, F32))
-            gu = ops.gemm_bf16(ops.NT, n2, Wgu, out=t("gu", 2 * ff))
-            h = ops.swiglu_fwd(gu, out=t("h", ff))
-            x2 = ops.gemm_bf16(ops.NT, h, Wd, out=t("x2", d), R=x1, epilogue=ops.EPI_RESID)
+            x1, n2, rstd2, gu, h, x2 = layer.attn_out_mlp_fwd(lw, x, attn, eps, dst)
             layers.append(dict(x=x, n1=n1, rstd1=rstd1, qkv=qkv, attn=attn, lse=lse, x1=x1, n2=n2, rstd2=rstd2, gu=gu, h=h))
             x = x2                                     # (dkv_acc needs no zero-fill: the first step SETS the prefix rows)
         P["layers"] = layers
@@ -753,36 +747,24 @@ class PrefixEpisode:
                 self._lse_ptrs[ks] = ops.h2d(torch.from_numpy(np.array([t_.data_ptr() for t_ in self.lse_s[ks]], np.int64)), m.device)
             s_lse = self._lse_ptrs[ks]
         layers = []
+        rows = slice(r0, r0 + M)               # this step's block of the episode buffers: kept for finish()
         for i in range(L):
-            Wqkv, Wo, Wgu, Wd, w1, w2 = self._weights(i)[:6]
+            lw = st.layer(i)
             E = self._E[i] if defer else None
-
-            def t(name, width, dt=BF16, E=E, i=i):
-                if E is not None and name in E:
-                    return E[name][r0:r0 + M]          # this step's block of the episode buffers: kept for finish()
-                if allm and name in ("r1", "r2"):
-                    return self._E32[i][name][r0:r0 + M]
-                if allm and name == "x2" and i + 1 < L:
-                    return self._E[i + 1]["x"][r0:r0 + M]
-                return self._buf(f"s{i}.{name}", (M, width) if width else (M,), dt)
-            n1, rstd1 = ops.rmsnorm_fwd(x, w1, eps, out=t("n1", d), rstd=t("r1", 0, F32))
+            dst = self._dst("s", i, rows, ("n1", "rstd1", "attn", "x1", "n2", "rstd2", "gu", "h", "x2"), E, allm)
+            n1, rstd1 = ops.rmsnorm_fwd(x, lw.w1, eps, out=dst["n1"], rstd=dst["rstd1"])
             # q|k|v with RoPE in the GEMM epilogue (bit-identical to the GEMM followed by nv_rope_rows_bf16), row r at position pos[r]
-            qkv = ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][r0:r0 + M] if allm else self._buf("qkv", (M, 3 * d)),
-                                    pos_i32=step["pos"])
-            attn = t("attn", d)
+            qkv = ops.qkv_rope(n1, lw.Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][rows] if allm else self._buf("qkv", (M, 3 * d)),
+                               pos_i32=step["pos"])
+            attn = dst["attn"]
             if epi:
                 ops.attn_fwd_episode(E["qkv"][:r0 + M], E["attn"][:r0 + M], s_lse[i:i + 1], self.prefix["cu"], s_tab, 1, B, H, hd, cap, step["N"])
             else:
                 ops.scatter_rows_bf16_(qkv, step["crow"], self.cache[i])
                 lse_i = self.lse_s[ks][i] if allm else self.lse[i]
                 ops.attn_fwd_strided(self.cache[i], self.kv0, B, Lmax, cap, H, hd, out=self.attn_buf[i], lse2=lse_i, q_row_min=qmin)
-                ops._lib.check(ops._L().nv_gather_rows_bf16(self.attn_buf[i].data_ptr(), step["grow"].data_ptr(), attn.data_ptr(), M, d, ops._st()),
-                               "nv_gather_rows_bf16")
-            x1 = ops.gemm_bf16(ops.NT, attn, Wo, out=t("x1", d), R=x, epilogue=ops.EPI_RESID)
-            n2, rstd2 = ops.rmsnorm_fwd(x1, w2, eps, out=t("n2", d), rstd=t("r2", 0, F32))
-            gu = ops.gemm_bf16(ops.NT, n2, Wgu, out=t("gu", 2 * ff))
-            h = ops.swiglu_fwd(gu, out=t("h", ff))
-            x2 = ops.gemm_bf16(ops.NT, h, Wd, out=t("x2", d), R=x1, epilogue=ops.EPI_RESID)
+                ops.gather_rows_bf16(self.attn_buf[i], step["grow"], out=attn)
+            x1, n2, rstd2, gu, h, x2 = layer.attn_out_mlp_fwd(lw, x, attn, eps, dst)
             if not allm:
                 layers.append(dict(x=x, n1=n1, rstd1=rstd1, attn=attn, x1=x1, n2=n2, rstd2=rstd2, gu=gu, h=h))
             x = x2
@@ -814,21 +796,15 @@ class PrefixEpisode:
         other = self._buf("dx_b", (M, d))
         zeros_md = self._buf("zeros_md", (M, d))
         zeros_md.zero_()
+        ff = cfg.intermediate_size
+        wgrad = layer.wgrad_deferred if defer else layer.wgrad_now(ops.EPI_ACCUM)
         for i in reversed(range(L)):
-            Wqkv, Wo, Wgu, Wd, w1, w2, gqkv, go, ggu, gd, gw1, gw2 = self._weights(i)
+            lw = st.layer(i)
             a = saved["layers"][i]
             E = self._E[i] if defer else None
-            dh = ops.gemm_bf16(ops.NN, dx, Wd, out=self._buf("dh", (M, cfg.intermediate_size)))
-            if not defer:
-                ops.gemm_bf16(ops.TN, dx, a["h"], out=gd, epilogue=ops.EPI_ACCUM)
-            dgu = ops.swiglu_bwd(a["gu"], dh, out=E["dgu"][rows] if defer else self._buf("dgu", (M, 2 * cfg.intermediate_size)))
-            dn2 = ops.gemm_bf16(ops.NN, dgu, Wgu, out=self._buf("dn2", (M, d)))
-            if not defer:
-                ops.gemm_bf16(ops.TN, dgu, a["n2"], out=ggu, epilogue=ops.EPI_ACCUM)
-            dx1 = ops.rmsnorm_bwd(dn2, a["x1"], w2, a["rstd2"], gw2, resid_grad=dx, out=E["dx1"][rows] if defer else self._buf("dx1", (M, d)))
-            dattn = ops.gemm_bf16(ops.NN, dx1, Wo, out=self._buf("dattn", (M, d)))
-            if not defer:
-                ops.gemm_bf16(ops.TN, dx1, a["attn"], out=go, epilogue=ops.EPI_ACCUM)
+            dst = {"dh": self._buf("dh", (M, ff)), "dgu": E["dgu"][rows] if defer else self._buf("dgu", (M, 2 * ff)), "dn2": self._buf("dn2", (M, d)),
+                   "dx1": E["dx1"][rows] if defer else self._buf("dx1", (M, d)), "dattn": self._buf("dattn", (M, d))}
+            dx1, dattn, _ = layer.attn_out_mlp_bwd(lw, dx, a["attn"], a["x1"], a["n2"], a["rstd2"], a["gu"], a["h"], dst, wgrad)
             # attention backward on the cache layout: dO is zero everywhere except this step's rows (written, used, zeroed again:
             # a full-buffer fill per layer was 3 % of the episode)
             ops.scatter_rows_bf16_(dattn, step["crow"], self.dout_full)
@@ -842,14 +818,11 @@ class PrefixEpisode:
             ops.rope_rows_t_(dqkv, m.rope_cos, m.rope_sin, step["pos"], H, hd)
             if not self.fuse_kvacc:
                 ops.kv_grad_accum(self.dqkv_full, self.dkv_acc[i], self.prefix["crow"], first=first)   # what this step sends into the prefix's K/V
-            dn1 = ops.gemm_bf16(ops.NN, dqkv, Wqkv, out=self._buf("dn1", (M, d)))
-            if not defer:
-                ops.gemm_bf16(ops.TN, dqkv, a["n1"], out=gqkv, epilogue=ops.EPI_ACCUM)
+            dst = {"dn1": self._buf("dn1", (M, d)), "dx": self._E[i - 1]["dxo"][rows] if defer and i > 0 else other}
+            ndx = layer.qkv_in_bwd(lw, dqkv, a["x"], a["n1"], a["rstd1"], dx1, dst, wgrad)
             if defer:
-                ndx = ops.rmsnorm_bwd(dn1, a["x"], w1, a["rstd1"], gw1, resid_grad=dx1, out=self._E[i - 1]["dxo"][rows] if i > 0 else other)
                 dx = ndx
             else:
-                ndx = ops.rmsnorm_bwd(dn1, a["x"], w1, a["rstd1"], gw1, resid_grad=dx1, out=other)
                 dx, other = ndx, dx
         self.prefix["kv_steps"] += 1
         dvis = ops.vis_grad(dx, step["vis_rows"]) if step["vis_rows"].numel() else None
@@ -895,44 +868,39 @@ class PrefixEpisode:
         R = self._cursor if defer else Mp               # token rows of the whole episode: prefix [0, Mp) + every step's block
         st.touch_layers()
         dx = None
+        ff = cfg.intermediate_size
+        wgrad = layer.wgrad_deferred if defer else layer.wgrad_now(ops.EPI_ACCUM)
         for i in reversed(range(L)):
-            Wqkv, Wo, Wgu, Wd, w1, w2, gqkv, go, ggu, gd, gw1, gw2 = self._weights(i)
+            lw = st.layer(i)
             a = P["layers"][i]
             E = self._E[i] if defer else None
             dqkv = E["dqkv"][:Mp] if defer else self._buf("p.dqkv", (Mp, 3 * d))
             dx1 = None
             if dx is not None:                    # (the top layer's prefix outputs feed nothing: only its K/V carry gradient)
-                dh = ops.gemm_bf16(ops.NN, dx, Wd, out=self._buf("p.dh", (Mp, cfg.intermediate_size)))
-                if not defer:
-                    ops.gemm_bf16(ops.TN, dx, a["h"], out=gd, epilogue=ops.EPI_ACCUM)
-                dgu = ops.swiglu_bwd(a["gu"], dh, out=E["dgu"][:Mp] if defer else self._buf("p.dgu", (Mp, 2 * cfg.intermediate_size)))
-                dn2 = ops.gemm_bf16(ops.NN, dgu, Wgu, out=self._buf("p.dn2", (Mp, d)))
-                if not defer:
-                    ops.gemm_bf16(ops.TN, dgu, a["n2"], out=ggu, epilogue=ops.EPI_ACCUM)
-                dx1 = ops.rmsnorm_bwd(dn2, a["x1"], w2, a["rstd2"], gw2, resid_grad=dx, out=E["dx1"][:Mp] if defer else self._buf("p.dx1", (Mp, d)))
-                dattn = ops.gemm_bf16(ops.NN, dx1, Wo, out=self._buf("p.dattn", (Mp, d)))
-                if not defer:
-                    ops.gemm_bf16(ops.TN, dx1, a["attn"], out=go, epilogue=ops.EPI_ACCUM)
+                dst = {"dh": self._buf("p.dh", (Mp, ff)), "dgu": E["dgu"][:Mp] if defer else self._buf("p.dgu", (Mp, 2 * ff)),
+                       "dn2": self._buf("p.dn2", (Mp, d)), "dx1": E["dx1"][:Mp] if defer else self._buf("p.dx1", (Mp, d)),
+                       "dattn": self._buf("p.dattn", (Mp, d))}
+                dx1, dattn, _ = layer.attn_out_mlp_bwd(lw, dx, a["attn"], a["x1"], a["n2"], a["rstd2"], a["gu"], a["h"], dst, wgrad)
                 ops.attn_bwd_varlen(a["qkv"], a["attn"], dattn, a["lse"], P["cu"], P["pos0"], B, Lmax, H, hd, dqkv, q_row_min=0, rope=None)
             else:
                 dqkv.zero_()
             ops.kv_grad_inject(dqkv, self.dkv_acc[i], P["crow"])
             ops.rope_rows_t_(dqkv, m.rope_cos, m.rope_sin, P["pos"], H, hd)
-            dn1 = ops.gemm_bf16(ops.NN, dqkv, Wqkv, out=self._buf("p.dn1", (Mp, d)))
+
+            wgrad_qkv = wgrad
             if defer:
-                # the episode's weight gradients of this layer: ONE GEMM per weight over every token row (prefix + all steps), fp32
-                # accumulation over the whole contraction.  The top layer's prefix rows carry no gradient outside q|k|v.
-                lo = 0 if dx is not None else Mp
-                if R > lo:
-                    ops.gemm_bf16(ops.TN, E["dxo"][lo:R], E["h"][lo:R], out=gd, epilogue=ops.EPI_ACCUM)
-                    ops.gemm_bf16(ops.TN, E["dgu"][lo:R], E["n2"][lo:R], out=ggu, epilogue=ops.EPI_ACCUM)
-                    ops.gemm_bf16(ops.TN, E["dx1"][lo:R], E["attn"][lo:R], out=go, epilogue=ops.EPI_ACCUM)
-                ops.gemm_bf16(ops.TN, E["dqkv"][:R], E["n1"][:R], out=gqkv, epilogue=ops.EPI_ACCUM)
-                dx = ops.rmsnorm_bwd(dn1, a["x"], w1, a["rstd1"], gw1, resid_grad=dx1,
-                                     out=self._E[i - 1]["dxo"][:Mp] if i > 0 else self._buf("p.dx0", (Mp, d)))
+                def wgrad_qkv(*_, lw=lw, E=E, lo=0 if dx is not None else Mp):
+                    """the episode's weight gradients of this layer: ONE GEMM per weight over every token row (prefix + all steps), fp32
+                    accumulation over the whole contraction.  The top layer's prefix rows carry no gradient outside q|k|v."""
+                    if R > lo:
+                        ops.gemm_bf16(ops.TN, E["dxo"][lo:R], E["h"][lo:R], out=lw.gd, epilogue=ops.EPI_ACCUM)
+                        ops.gemm_bf16(ops.TN, E["dgu"][lo:R], E["n2"][lo:R], out=lw.ggu, epilogue=ops.EPI_ACCUM)
+                        ops.gemm_bf16(ops.TN, E["dx1"][lo:R], E["attn"][lo:R], out=lw.go, epilogue=ops.EPI_ACCUM)
+                    ops.gemm_bf16(ops.TN, E["dqkv"][:R], E["n1"][:R], out=lw.gqkv, epilogue=ops.EPI_ACCUM)
+                dx_out = self._E[i - 1]["dxo"][:Mp] if i > 0 else self._buf("p.dx0", (Mp, d))
             else:
-                ops.gemm_bf16(ops.TN, dqkv, a["n1"], out=gqkv, epilogue=ops.EPI_ACCUM)
-                dx = ops.rmsnorm_bwd(dn1, a["x"], w1, a["rstd1"], gw1, resid_grad=dx1, out=self._buf(f"p.dx{i & 1}", (Mp, d)))
+                dx_out = self._buf(f"p.dx{i & 1}", (Mp, d))
+            dx = layer.qkv_in_bwd(lw, dqkv, a["x"], a["n1"], a["rstd1"], dx1, {"dn1": self._buf("p.dn1", (Mp, d)), "dx": dx_out}, wgrad_qkv)
             m._dp_layer_done(i, [])
         if defer:
             self._last_rows = R - Mp
@@ -1028,10 +996,10 @@ class PrefixEpisode:
                 self._fill_prefix_cache(P)             # the prefix went through the decoder earlier: its K/V rows into the cache layout
             x = ops.embed_vis(st.p("lang_model.model.embed_tokens.weight"), ids_cat, vix_cat, vis_cat, out=self._E[0]["x"][rows])
             for i in range(L):
-                Wqkv, Wo, Wgu, Wd, w1, w2 = self._weights(i)[:6]
+                lw = st.layer(i)
                 E, E32 = self._E[i], self._E32[i]
-                n1, _ = ops.rmsnorm_fwd(x, w1, eps, out=E["n1"][rows], rstd=E32["r1"][rows])
-                ops.qkv_rope(n1, Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][rows], pos_i32=pos_cat)
+                n1, _ = ops.rmsnorm_fwd(x, lw.w1, eps, out=E["n1"][rows], rstd=E32["r1"][rows])
+                ops.qkv_rope(n1, lw.Wqkv, m.rope_cos, m.rope_sin, cap, H, hd, out=E["qkv"][rows], pos_i32=pos_cat)
                 if pend:
                     # the prefix rows' own causal attention (the top layer's is never read: only its K/V are, by the steps' queries)
                     if i < L - 1 or not prune_top:
@@ -1046,28 +1014,20 @@ class PrefixEpisode:
                     ops.scatter_rows_bf16_(E["qkv"][sl], sp["crow"], self.cache[i])
                     ops.attn_fwd_strided(self.cache[i], self.kv0, self.B, sp["Lmax"], cap, H, hd, out=self.attn_buf[i], lse2=self.lse_s[r["k"]][i],
                                          q_row_min=sp["qmin"])
-                    ops._lib.check(ops._L().nv_gather_rows_bf16(self.attn_buf[i].data_ptr(), sp["grow"].data_ptr(), E["attn"][sl].data_ptr(),
-                                                                sp["M"], d, ops._st()), "nv_gather_rows_bf16")
+                    ops.gather_rows_bf16(self.attn_buf[i], sp["grow"], out=E["attn"][sl])
                 if i == L - 1 and prune_top:
                     # the top layer feeds only each sample's LAST row of every step (nav_model.py:237) -- after its K/V projection and
                     # attention, o_proj / MLP run on those T*B rows instead of on every suffix row (what LlamaStack's pruned last layer
                     # does on the recompute path); the batched backward mirrors it (`top`)
                     x_l = ops.gather_rows_bf16(x, last_x)
                     attn_l = ops.gather_rows_bf16(E["attn"][rows], last_x)
-                    x1_l = ops.gemm_bf16(ops.NT, attn_l, Wo, R=x_l, epilogue=ops.EPI_RESID)
-                    n2_l, r2_l = ops.rmsnorm_fwd(x1_l, w2, eps)
-                    gu_l = ops.gemm_bf16(ops.NT, n2_l, Wgu)
-                    h_l = ops.swiglu_fwd(gu_l)
-                    x_last = ops.gemm_bf16(ops.NT, h_l, Wd, R=x1_l, epilogue=ops.EPI_RESID)
+                    x1_l, n2_l, r2_l, gu_l, h_l, x_last = layer.attn_out_mlp_fwd(lw, x_l, attn_l, eps)
                     top_now = dict(idx=last_cat, attn=attn_l, x1=x1_l, n2=n2_l, r2=r2_l, gu=gu_l, h=h_l)
                     P.setdefault("tops", []).append(top_now)
                     break
-                x1 = ops.gemm_bf16(ops.NT, E["attn"][rows], Wo, out=E["x1"][rows], R=x, epilogue=ops.EPI_RESID)
-                n2, _ = ops.rmsnorm_fwd(x1, w2, eps, out=E["n2"][rows], rstd=E32["r2"][rows])
-                gu = ops.gemm_bf16(ops.NT, n2, Wgu, out=E["gu"][rows])
-                h = ops.swiglu_fwd(gu, out=E["h"][rows])
-                x = ops.gemm_bf16(ops.NT, h, Wd, out=self._E[i + 1]["x"][rows] if i + 1 < L else self._buf("lz.x2", (max(R, self._ecap), d))[:R - r_lo], R=x1,
-                                  epilogue=ops.EPI_RESID)
+                dst = {"x1": E["x1"][rows], "n2": E["n2"][rows], "rstd2": E32["r2"][rows], "gu": E["gu"][rows], "h": E["h"][rows],
+                       "x2": self._E[i + 1]["x"][rows] if i + 1 < L else self._buf("lz.x2", (max(R, self._ecap), d))[:R - r_lo]}
+                x = layer.attn_out_mlp_fwd(lw, x, E["attn"][rows], eps, dst)[5]
             if top_now is None:
                 x_last = ops.gather_rows_bf16(x, last_x)
             if pend:
@@ -1267,8 +1227,9 @@ class PrefixEpisode:
                     recs[-1]["r0"] + recs[-1]["step"]["M"] == R, "the steps' blocks must tile rows [Mp, R) of the episode buffers"
             if epi_tab is None and recs:
                 self._fill_prefix_cache(P)                   # the per-step backward form reads the prefix's K/V from the K/V-cache layout
+            wgrad = layer.wgrad_now(wacc)
             for i in reversed(range(L)):
-                Wqkv, Wo, Wgu, Wd, w1, w2, gqkv, go, ggu, gd, gw1, gw2 = self._weights(i)
+                lw = st.layer(i)
                 E, E32 = self._E[i], self._E32[i]
                 # the top layer's prefix rows feed nothing (only their K/V carry gradient): its MLP / o_proj backward covers the steps' rows
                 # only; a segment flush (final=False) never touches the prefix rows
@@ -1276,27 +1237,15 @@ class PrefixEpisode:
                 if i == L - 1 and top is not None:
                     # the pruned tail's backward on the T*B last rows; what flows on into the attention output / the residual stream is
                     # zero everywhere else
-                    dh_l = ops.gemm_bf16(ops.NN, dxl, Wd)
-                    ops.gemm_bf16(ops.TN, dxl, top["h"], out=gd, epilogue=wacc)
-                    dgu_l = ops.swiglu_bwd(top["gu"], dh_l)
-                    dn_l = ops.gemm_bf16(ops.NN, dgu_l, Wgu)
-                    ops.gemm_bf16(ops.TN, dgu_l, top["n2"], out=ggu, epilogue=wacc)
-                    dx1_l = ops.rmsnorm_bwd(dn_l, top["x1"], w2, top["r2"], gw2, resid_grad=dxl)
-                    dattn_l = ops.gemm_bf16(ops.NN, dx1_l, Wo)
-                    ops.gemm_bf16(ops.TN, dx1_l, top["attn"], out=go, epilogue=wacc)
+                    dx1_l, dattn_l, _ = layer.attn_out_mlp_bwd(lw, dxl, top["attn"], top["x1"], top["n2"], top["r2"], top["gu"], top["h"], wgrad=wgrad)
                     dattn[Mp:].zero_()
                     dx1[Mp:].zero_()
                     ops.scatter_rows_bf16_(dattn_l, top["idx"], dattn[Mp:])
                     ops.scatter_rows_bf16_(dx1_l, top["idx"], dx1[Mp:])
                 elif R > lo:
-                    ops.gemm_bf16(ops.NN, dx[lo:], Wd, out=dh[lo:])
-                    ops.gemm_bf16(ops.TN, dx[lo:], E["h"][lo:R], out=gd, epilogue=wacc)
-                    ops.swiglu_bwd(E["gu"][lo:R], dh[lo:], out=dgu[lo:])
-                    ops.gemm_bf16(ops.NN, dgu[lo:], Wgu, out=dn[lo:])
-                    ops.gemm_bf16(ops.TN, dgu[lo:], E["n2"][lo:R], out=ggu, epilogue=wacc)
-                    ops.rmsnorm_bwd(dn[lo:], E["x1"][lo:R], w2, E32["r2"][lo:R], gw2, resid_grad=dx[lo:], out=dx1[lo:])
-                    ops.gemm_bf16(ops.NN, dx1[lo:], Wo, out=dattn[lo:])
-                    ops.gemm_bf16(ops.TN, dx1[lo:], E["attn"][lo:R], out=go, epilogue=wacc)
+                    dst = {"dh": dh[lo:], "dgu": dgu[lo:], "dn2": dn[lo:], "dx1": dx1[lo:], "dattn": dattn[lo:]}
+                    layer.attn_out_mlp_bwd(lw, dx[lo:], E["attn"][lo:R], E["x1"][lo:R], E["n2"][lo:R], E32["r2"][lo:R], E["gu"][lo:R], E["h"][lo:R],
+                                           dst, wgrad)
                 # attention backward.  The prefix rows' own causal attention (packed rows) ...
                 if final:
                     if lo == 0:
@@ -1321,9 +1270,7 @@ class PrefixEpisode:
                 else:
                     q0 = Mp
                 if R > q0:
-                    ops.gemm_bf16(ops.NN, dqkv[q0:], Wqkv, out=dn[q0:])
-                    ops.gemm_bf16(ops.TN, dqkv[q0:], E["n1"][q0:R], out=gqkv, epilogue=wacc)
-                    ops.rmsnorm_bwd(dn[q0:], E["x"][q0:R], w1, E32["r1"][q0:R], gw1, resid_grad=dx1[q0:], out=other[q0:])
+                    layer.qkv_in_bwd(lw, dqkv[q0:], E["x"][q0:R], E["n1"][q0:R], E32["r1"][q0:R], dx1[q0:], {"dn1": dn[q0:], "dx": other[q0:]}, wgrad)
                 dx, other = other, dx
                 if final:
                     m._dp_layer_done(i, [])

@@ -11,10 +11,17 @@ fp32 tensors in ONE fp32 buffer (same for gradients and both AdamW moments).  Co
 `nn.Parameter`s named exactly like the reference's state_dict (navillm_amd/params.py) are views
 into these buffers, so `state_dict()/load_state_dict()` keep working (tools/optims.py:12-24,65-78).
 """
+from collections import namedtuple
+
 import torch
 from .params import param_specs
 
 ALIGN = 64  # elements; keeps every tensor 128-B aligned for 16-B vector access and DMA
+
+# one decoder layer's operands as views of the flat buffers (FlatStore.layer): the four packed GEMM weights, the two RMSNorm
+# weights, and the gradient view of each.  The weights are None once to_fp8_weight_only() released them, the gradients once
+# the gradient buffers are gone.
+LayerOperands = namedtuple("LayerOperands", "Wqkv Wo Wgu Wd w1 w2 gqkv go ggu gd gw1 gw2")
 
 
 def _lm_order(cfg):
@@ -78,12 +85,12 @@ class FlatStore:
         self.exp_avg_sq = None
         self.master = None        # {"lm": fp32 master weights} under FlatAdamW(state_precision="fp32_master"), else None
         self._upd = None          # an AdamW update of the LM group still running on the optimizer's side stream (FlatAdamW.step, round 6)
+        self._layers = {}         # layer index -> LayerOperands; dropped wherever the flat buffers are replaced or released
 
     # ---- asynchronous update of the LM group (navillm_amd/optim.py::FlatAdamW.step with overlap): the update kernels run on a side stream,
     # decoder layer by decoder layer in flat order, while the launch stream goes on with the next episode's scene-encoder / fusion steps
     # (fp32 group: updated on the launch stream itself).  Whoever touches LM-group parameters OR gradients next waits for exactly the
-    # part it needs: every accessor below (`p`, `g`, `qkv`, `gate_up`, `lm_head_padded`) and `PrefixEpisode._weights` calls
-    # `wait_params`; code that reads the raw buffers (`state_dict`, the native decoder's pointer table, the DP broadcast, the next clip /
+    # part it needs: every accessor below (`p`, `g`, `qkv`, `gate_up`, `layer`, `lm_head_padded`) calls `wait_params`; code that reads the raw buffers (`state_dict`, the native decoder's pointer table, the DP broadcast, the next clip /
     # step, a full zero_grad) calls it without arguments = waits for all of it.  Other streams (the DP exchange, the wgrad side stream)
     # fork from the launch stream AFTER it has waited, so they inherit the order.
     def begin_async_update(self, stream, head_ev, layer_evs, done_ev, home):
@@ -161,6 +168,22 @@ class FlatStore:
         assert v.shape[0] == 2 * self.cfg.intermediate_size, "gate/up must be adjacent and unpadded"
         return v
 
+    def layer(self, i):
+        """decoder layer i's LayerOperands, built once.  Like every accessor, each fetch orders the current stream behind a pending
+        side-stream update of that layer.  The views stay valid while the flat buffers do: `.to()` is refused (NavModel._apply), loading
+        a state_dict copies in place, and the two release_* methods below drop the cache."""
+        if self._upd is not None:
+            self.wait_params(layer=i)
+        rec = self._layers.get(i)
+        if rec is None:
+            p = f"lang_model.model.layers.{i}."
+            o, d, n1, n2 = p + "self_attn.o_proj.weight", p + "mlp.down_proj.weight", p + "input_layernorm.weight", p + "post_attention_layernorm.weight"
+            W = (None,) * 4 if o in getattr(self, "released", ()) else (self.qkv(i), self.p(o), self.gate_up(i), self.p(d))
+            G = (None,) * 6 if self.grad is None else (self.qkv(i, grad=True), self.g(o), self.gate_up(i, grad=True), self.g(d),
+                                                       self.g(n1), self.g(n2))
+            rec = self._layers[i] = LayerOperands(*W, self.p(n1), self.p(n2), *G)
+        return rec
+
     def lm_head_padded(self, grad=False):
         o = self.offsets["lang_model.lm_head.weight"]
         d = self.cfg.hidden_size
@@ -224,6 +247,7 @@ class FlatStore:
         for n in keep:
             new[new_off[n]:new_off[n] + self.alloc_sizes[n]].copy_(self.param["lm"][self.offsets[n]:self.offsets[n] + self.alloc_sizes[n]])
         self.param["lm"] = new
+        self._layers = {}
         self.offsets.update(new_off)
         self.released = {n for n in self.names["lm"] if gone(n)}
         self.names["lm"] = keep
@@ -238,6 +262,7 @@ class FlatStore:
     def release_grads(self, named_params):
         """inference deployment that keeps the parameters: drop the gradient buffers and the optimizer state only"""
         self.grad = None
+        self._layers = {}
         self.exp_avg = self.exp_avg_sq = self.master = None
         for p in named_params.values():
             p.grad = None

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import torch
 from . import debug
+from . import layer
 from . import ops
 
 F32, BF16 = torch.float32, torch.bfloat16
@@ -423,36 +424,29 @@ class LlamaStack(torch.autograd.Function):
                 return ops.attn_fwd_varlen(qkv, cu, kv_start_i32, B, Sm, H, hd, out=a["attn"][:M], lse2=lse, q_row_min=qmin)
             return ops.attn_fwd(qkv, kv_start_i32, B, S, H, hd, out=a["attn"][:M], lse2=lse, q_row_min=max(qmin, 0))
 
+        def lm_linear(i):
+            """layer i's Linear through NavModel.lm_linear: the bf16 operands or their weight-only fp8 form"""
+            return lambda a_, kind, **kw: model.lm_linear(a_, i, kind, **kw)
+
         L_full = cfg.num_layers - (1 if tail_rows is not None else 0)
         for i in range(L_full):
-            p = f"lang_model.model.layers.{i}."
-            a = ar.layers[i]
-            n1, rstd1 = ops.rmsnorm_fwd(x, st.p(p + "input_layernorm.weight"), eps, out=a["n1"][:M], rstd=a["rstd1"][:M])
+            lw, a = st.layer(i), ar.layers[i]
+            n1, rstd1 = ops.rmsnorm_fwd(x, lw.w1, eps, out=a["n1"][:M], rstd=a["rstd1"][:M])
             qkv = qkv_proj(n1, i, a)
             attn, lse = attention(qkv, a, 0)
-            x1 = model.lm_linear(attn, i, "o", out=a["x1"][:M], R=x, epilogue=ops.EPI_RESID)
-            n2, rstd2 = ops.rmsnorm_fwd(x1, st.p(p + "post_attention_layernorm.weight"), eps, out=a["n2"][:M],
-                                        rstd=a["rstd2"][:M])
-            gu = model.lm_linear(n2, i, "gate_up", out=a["gu"][:M])
-            h = ops.swiglu_fwd(gu, out=a["h"][:M])
-            x = model.lm_linear(h, i, "down", out=a["x2"][:M], R=x1, epilogue=ops.EPI_RESID)
+            x = layer.attn_out_mlp_fwd(lw, x, attn, eps, {k: a[k][:M] for k in ("x1", "n2", "rstd2", "gu", "h", "x2")}, lm_linear(i))[5]
         ctx.tail = None
         if tail_rows is not None:
             i = cfg.num_layers - 1
-            p = f"lang_model.model.layers.{i}."
-            a = ar.layers[i]
+            lw, a = st.layer(i), ar.layers[i]
             # padded layout: every sample ends at row S-1 -> one global first query row; packed: per sample (-1)
             qmin = -1 if cu is not None else ((S - 1) // 128) * 128
-            n1, _ = ops.rmsnorm_fwd(x, st.p(p + "input_layernorm.weight"), eps, out=a["n1"][:M], rstd=a["rstd1"][:M])
+            n1, _ = ops.rmsnorm_fwd(x, lw.w1, eps, out=a["n1"][:M], rstd=a["rstd1"][:M])
             qkv = qkv_proj(n1, i, a)
             attn, _ = attention(qkv, a, qmin)
             attn_r = ops.gather_rows_bf16(attn, tail_rows)
             x_r = ops.gather_rows_bf16(x, tail_rows)
-            x1_r = model.lm_linear(attn_r, i, "o", R=x_r, epilogue=ops.EPI_RESID)
-            n2_r, rstd2_r = ops.rmsnorm_fwd(x1_r, st.p(p + "post_attention_layernorm.weight"), eps)
-            gu_r = model.lm_linear(n2_r, i, "gate_up")
-            h_r = ops.swiglu_fwd(gu_r)
-            x = model.lm_linear(h_r, i, "down", R=x1_r, epilogue=ops.EPI_RESID)
+            x1_r, n2_r, rstd2_r, gu_r, h_r, x = layer.attn_out_mlp_fwd(lw, x_r, attn_r, eps, linear=lm_linear(i))
             ctx.tail = (tail_rows, qmin, attn_r, x1_r, rstd2_r, n2_r, gu_r, h_r, x)
         Hs, rstdf = ops.rmsnorm_fwd(x, st.p("lang_model.model.norm.weight"), eps)
         ctx.model, ctx.E, ctx.rstdf = model, E, rstdf
@@ -491,35 +485,27 @@ class LlamaStack(torch.autograd.Function):
             rows, qmin, attn_r, x1_r, rstd2_r, n2_r, gu_r, h_r, x2_r = ctx.tail
             i = L - 1
             L_full = L - 1
-            p = f"lang_model.model.layers.{i}."
-            a = ar.layers[i]
+            lw, a = st.layer(i), ar.layers[i]
             x = ctx.E if i == 0 else ar.layers[i - 1]["x2"][:M]
             n1, qkv, attn = a["n1"][:M], a["qkv"][:M], a["attn"][:M]
             lse = a["lse"][:B * H * Sm].view(B, H, Sm)
             dx2_r = ops.rmsnorm_bwd(_c(dH), x2_r, st.p("lang_model.model.norm.weight"), ctx.rstdf,
                                     st.g("lang_model.model.norm.weight"))
-            dh_r = ops.gemm_bf16(ops.NN, dx2_r, st.p(p + "mlp.down_proj.weight"))
-            ops.gemm_bf16(ops.TN, dx2_r, h_r, out=st.g(p + "mlp.down_proj.weight"), epilogue=WACC)
-            dgu_r = ops.swiglu_bwd(gu_r, dh_r)
-            dn2_r = ops.gemm_bf16(ops.NN, dgu_r, st.gate_up(i))
-            ops.gemm_bf16(ops.TN, dgu_r, n2_r, out=st.gate_up(i, grad=True), epilogue=WACC)
-            dx1_r = ops.rmsnorm_bwd(dn2_r, x1_r, st.p(p + "post_attention_layernorm.weight"), rstd2_r,
-                                    st.g(p + "post_attention_layernorm.weight"), resid_grad=dx2_r)
-            dattn_r = ops.gemm_bf16(ops.NN, dx1_r, st.p(p + "self_attn.o_proj.weight"))
-            ops.gemm_bf16(ops.TN, dx1_r, attn_r, out=st.g(p + "self_attn.o_proj.weight"), epilogue=WACC)
+            dx1_r, dattn_r, _ = layer.attn_out_mlp_bwd(lw, dx2_r, attn_r, x1_r, n2_r, rstd2_r, gu_r, h_r, wgrad=layer.wgrad_now(WACC))
             dattn = sc["dattn"]
             dattn.zero_()
             ops.scatter_rows_bf16_(dattn_r, rows, dattn)
             dqkv = sc["dqkv"]
             dqkv.zero_()                       # dQ rows below qmin are not written by the kernel
             attention_bwd(qkv, attn, dattn, lse, dqkv, qmin)
-            dn1 = ops.gemm_bf16(ops.NN, dqkv, st.qkv(i), out=sc["dn1"])
-            ops.gemm_bf16(ops.TN, dqkv, n1, out=st.qkv(i, grad=True), epilogue=WACC)
             resid = sc["dx1"]
-            resid.zero_()
-            ops.scatter_rows_bf16_(dx1_r, rows, resid)
-            dx = ops.rmsnorm_bwd(dn1, x, st.p(p + "input_layernorm.weight"), a["rstd1"][:M], st.g(p + "input_layernorm.weight"),
-                                 resid_grad=resid, out=sc["dxa"])
+
+            def spread_resid(_):
+                """the B rows of dx1 into the full-size residual gradient, where it has always run: behind the q|k|v weight gradient"""
+                resid.zero_()
+                ops.scatter_rows_bf16_(dx1_r, rows, resid)
+            dx = layer.qkv_in_bwd(lw, dqkv, x, n1, a["rstd1"][:M], resid, {"dn1": sc["dn1"], "dx": sc["dxa"]}, layer.wgrad_now(WACC),
+                                  before_write=spread_resid)
             model._dp_layer_done(i, [])
         else:
             xL = ar.layers[L - 1]["x2"][:M]
@@ -542,26 +528,28 @@ class LlamaStack(torch.autograd.Function):
         # nav-steps/s, ABAB): two 256x256-tile GEMMs sharing the CUs evict each other's panels from the XCD L2s.
         pair = side is not None and model.overlap_wgrad == 2
 
+        pre, ev = None, []              # (pair mode) the event of the last mark(); the layer's side-stream wgrad events (for the DP exchange)
+        dx_name, nxt_name = "dxa", "dxb"
+
         def mark():
             """(pair mode) event on the chain before a dgrad GEMM is launched: its dY is ready from here on"""
-            if not pair:
-                return None
-            e = torch.cuda.Event()
-            e.record(main)
-            return e
+            nonlocal pre
+            if pair:
+                pre = torch.cuda.Event()
+                pre.record(main)
 
-        def wgrad(dy_name, dy, act, gout, pre=None):
-            if side is None:
-                ops.gemm_bf16(ops.TN, dy, act, out=gout, epilogue=WACC)
-                return None
+        def wgrad(name, dy, act, gout):
+            """on the side stream (without one the plain GEMM of layer.wgrad_now runs instead, see `hooks`)"""
+            nonlocal pre
             if pair:
                 side.wait_event(pre)
+                pre = None
                 with torch.cuda.stream(side):
                     ops.gemm_bf16(ops.TN, dy, act, out=gout, epilogue=WACC)
                     done = torch.cuda.Event()
                     done.record(side)
                 main.wait_event(done)                          # the chain's next kernel starts after BOTH GEMMs
-                return None
+                return
             e = torch.cuda.Event()
             e.record(main)
             side.wait_event(e)
@@ -569,53 +557,29 @@ class LlamaStack(torch.autograd.Function):
                 ops.gemm_bf16(ops.TN, dy, act, out=gout, epilogue=WACC)
                 done = torch.cuda.Event()
                 done.record(side)
-            last_read[dy_name] = done
-            return done
+            # the scratch buffer that holds this wgrad's dY
+            last_read[{"down": dx_name, "gate_up": "dgu", "o": "dx1", "qkv": "dqkv"}[name]] = done
+            ev.append(done)
 
         def before_write(name):
-            ev = last_read.pop(name, None)
-            if ev is not None:
-                main.wait_event(ev)
+            e = last_read.pop(nxt_name if name == "dx" else name, None)
+            if e is not None:
+                main.wait_event(e)
 
-        dx_name, nxt_name = "dxa", "dxb"
+        hooks = dict(wgrad=wgrad, mark=mark, before_write=before_write) if side is not None else dict(wgrad=layer.wgrad_now(WACC))
         for i in reversed(range(L_full)):
-            p = f"lang_model.model.layers.{i}."
-            a = ar.layers[i]
+            lw, a = st.layer(i), ar.layers[i]
             x = ctx.E if i == 0 else ar.layers[i - 1]["x2"][:M]
             n1, qkv, attn, x1, n2, gu, h = (a[k][:M] for k in ("n1", "qkv", "attn", "x1", "n2", "gu", "h"))
             lse = a["lse"][:B * H * Sm].view(B, H, Sm)
-            Wd, Wo = st.p(p + "mlp.down_proj.weight"), st.p(p + "self_attn.o_proj.weight")
-            if FUSE_SWIGLU_BWD:
-                # dh = dx @ Wd never reaches HBM: the dgrad GEMM's epilogue applies SwiGLU' and writes d(gate|up) directly
-                before_write("dgu")
-                dgu = ops.gemm_bf16(ops.NN, dx, Wd, out=sc["dgu"], R=gu, epilogue=ops.EPI_SWIGLU_BWD)
-                ev = [wgrad(dx_name, dx, h, st.g(p + "mlp.down_proj.weight"))]
-            else:
-                pre = mark()
-                dh = ops.gemm_bf16(ops.NN, dx, Wd, out=sc["dh"])
-                ev = [wgrad(dx_name, dx, h, st.g(p + "mlp.down_proj.weight"), pre)]
-                before_write("dgu")
-                dgu = ops.swiglu_bwd(gu, dh, out=sc["dgu"])
-            pre = mark()
-            dn2 = ops.gemm_bf16(ops.NN, dgu, st.gate_up(i), out=sc["dn2"])
-            ev.append(wgrad("dgu", dgu, n2, st.gate_up(i, grad=True), pre))
-            before_write("dx1")
-            dx1 = ops.rmsnorm_bwd(dn2, x1, st.p(p + "post_attention_layernorm.weight"), a["rstd2"][:M],
-                                  st.g(p + "post_attention_layernorm.weight"), resid_grad=dx, out=sc["dx1"])
-            pre = mark()
-            dattn = ops.gemm_bf16(ops.NN, dx1, Wo, out=sc["dattn"])
-            ev.append(wgrad("dx1", dx1, attn, st.g(p + "self_attn.o_proj.weight"), pre))
+            ev = []
+            dx1, dattn, _ = layer.attn_out_mlp_bwd(lw, dx, attn, x1, n2, a["rstd2"][:M], gu, h, sc, fuse_swiglu=FUSE_SWIGLU_BWD, **hooks)
             before_write("dqkv")
             dqkv = attention_bwd(qkv, attn, dattn, lse, sc["dqkv"], 0)
-            pre = mark()
-            dn1 = ops.gemm_bf16(ops.NN, dqkv, st.qkv(i), out=sc["dn1"])
-            ev.append(wgrad("dqkv", dqkv, n1, st.qkv(i, grad=True), pre))
-            before_write(nxt_name)
-            ndx = ops.rmsnorm_bwd(dn1, x, st.p(p + "input_layernorm.weight"), a["rstd1"][:M], st.g(p + "input_layernorm.weight"),
-                                  resid_grad=dx1, out=nxt)
+            ndx = layer.qkv_in_bwd(lw, dqkv, x, n1, a["rstd1"][:M], dx1, {"dn1": sc["dn1"], "dx": nxt}, **hooks)
             dx, nxt = ndx, dx
             dx_name, nxt_name = nxt_name, dx_name
-            model._dp_layer_done(i, [e_ for e_ in ev if e_ is not None])
+            model._dp_layer_done(i, ev)
         out = sc["dE"]
         out.copy_(dx)
         if side is not None:
