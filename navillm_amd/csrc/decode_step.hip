@@ -6,6 +6,8 @@
 // (lm_head -> pick -> advance -> embed -> 32 decoder layers) has frozen launch arguments and is replayed from a hipGraph
 // (navillm_amd/kvcache.py); the host only polls the `fin` flags, a step or two behind.
 // Sampled decoding (HF sample(): temperature, top-k, top-p, one draw per row) is the same step with decode_pick_sample_kernel as its pick.
+// HF's repetition penalty and minimum length (PickProcs below; the rule is stated once) are the PROC = true
+// instantiations of the same three pick kernels; PROC = false is the pick without them.
 //
 // state layout (int32, one buffer): tok[B] | fin[B] | len[B] | pos[B] | crow[B] | grow[B] | last[B] | dyn[2] | cnt[1] | overflow[1]
 #include "nv_common.h"
@@ -65,34 +67,67 @@ __device__ __forceinline__ bool pick_emit(int* __restrict__ state, int* __restri
     return was;
 }
 
+// ---- the logits processors (HF's RepetitionPenaltyLogitsProcessor, then MinNewTokensLengthLogitsProcessor), applied after the special-id
+// mask and in front of everything else a pick does; DESIGN.md §4 "Logits processors" states the rule.
+//   seen [B, seen_ld] (nullable: no penalty): bit v & 31 of word v >> 5 of row b says that id v is in row b's own sequence (its
+//           unpadded prompt and what it emitted while unfinished).  The logit of such an id becomes bf16(x * pen) when x < 0, else
+//           bf16(x / pen) (fp32, correctly rounded divide, round-to-nearest-even back to bf16; -inf stays -inf, a NaN stays a NaN):
+//           a bf16 value again, so the 16-bit keys of the sampled pick stay exact.  Every pass of every pick applies it where it turns
+//           a loaded logit into a float, so all passes see the same penalised row.
+//   min_new while cnt < min_new, `eos` is no candidate.
+// After the pick thread 0 of the row's block sets the emitted token's bit, unless the row had finished before this step: one block owns
+// one row, so a plain load-or-store does and nothing depends on the order in which blocks arrive.
+struct PickProcs {
+    unsigned* seen;
+    int seen_ld;
+    float pen;
+    int min_new;
+};
+__device__ __forceinline__ float proc_penalise(float x, float pen) {
+    return x != x ? x : rbf(x < 0.f ? x * pen : __fdiv_rn(x, pen));
+}
+__device__ __forceinline__ bool proc_hit(const unsigned* seen_row, int v) { return seen_row && ((seen_row[v >> 5] >> (v & 31)) & 1u); }
+__device__ __forceinline__ void proc_mark(const PickProcs& pp, int b, int t, int V) {
+    if (pp.seen && t >= 0 && t < V) pp.seen[(long)b * pp.seen_ld + (t >> 5)] |= 1u << (t & 31);
+}
+
 // grid B, 1024 threads, 8 logits per load: argmax over the valid vocabulary (ids >= V and the special range are excluded; ties ->
 // smallest id, like torch.argmax on the CPU), then HF's bookkeeping: finished rows emit `pad`; a row finishes when it emits `eos`.
 constexpr int PICK_T = 1024;
+template <bool PROC>
 __global__ __launch_bounds__(PICK_T) void decode_pick_kernel(const bf16_t* __restrict__ logits, int ldl, int V, int special0, int nspecial,
                                                              int* __restrict__ state, int* __restrict__ out, int max_steps, int B, int eos,
-                                                             int pad) {
+                                                             int pad, PickProcs pp) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const bf16_t* row = logits + (long)b * ldl;
+    const unsigned* srow = (PROC && pp.seen) ? pp.seen + (long)b * pp.seen_ld : nullptr;
+    const bool ban = PROC && state[7 * B + 2] < pp.min_new;          // `eos` is no candidate yet
     float best = -INFINITY;
     int bi = PICK_NONE, be = 0;
-    auto take = [&](float x, int v) {
-        if (pick_allowed(v, V, special0, nspecial) && pick_beats(x, v, best, bi)) { best = x; bi = v; }
+    auto take = [&](float x, int v, bool hit) {
+        if (!pick_allowed(v, V, special0, nspecial) || (PROC && ban && v == eos)) return;
+        if (PROC && hit) x = proc_penalise(x, pp.pen);
+        if (pick_beats(x, v, best, bi)) { best = x; bi = v; }
     };
     const bool vec = ((ldl & 7) == 0) && ((((uintptr_t)logits) & 15) == 0);
     if (vec) {
         for (int v0 = tid * 8; v0 < V; v0 += PICK_T * 8) {
             const u32x4 q = *(const u32x4*)(row + v0);                 // ldl >= V rounded up by the caller's padding (vocab_pad % 8 == 0)
+            const unsigned w = srow ? srow[v0 >> 5] >> (v0 & 31) : 0u;  // v0 % 8 == 0: the eight ids share one word (v0 < V: inside seen_ld)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                take(__uint_as_float(q[j] << 16), v0 + 2 * j);
-                take(__uint_as_float(q[j] & 0xffff0000u), v0 + 2 * j + 1);
+                take(__uint_as_float(q[j] << 16), v0 + 2 * j, (w >> (2 * j)) & 1u);
+                take(__uint_as_float(q[j] & 0xffff0000u), v0 + 2 * j + 1, (w >> (2 * j + 1)) & 1u);
             }
         }
     } else {
-        for (int v = tid; v < V; v += PICK_T) take(bf2f(row[v]), v);
+        for (int v = tid; v < V; v += PICK_T) take(bf2f(row[v]), v, PROC && proc_hit(srow, v));
     }
     pick_reduce<PICK_T, false>(best, bi, be);
-    if (tid == 0) pick_emit(state, out, max_steps, B, b, bi, eos, pad);
+    if (tid == 0) {
+        const bool was = pick_emit(state, out, max_steps, B, b, bi, eos, pad);
+        if (PROC && !was) proc_mark(pp, b, bi, V);
+    }
 }
 
 // The same pick over the CHILDREN of a trie node (TrieLogitsProcessor, models/modified_lm.py:10-30, with the trie flattened by
@@ -103,13 +138,15 @@ __global__ __launch_bounds__(PICK_T) void decode_pick_kernel(const bf16_t* __res
 // token ids < 0 and successors outside [0, n_nodes) are skipped.  A node that is left with NO pickable child (all >= V or special;
 // kvcache.py keeps such tries on the host loop) emits `eos`, which finishes the row, and keeps its node.
 constexpr int TRIE_T = 256;
+template <bool PROC>
 __global__ __launch_bounds__(TRIE_T) void decode_pick_trie_kernel(const bf16_t* __restrict__ logits, int ldl, int V, int special0,
                                                                   int nspecial, const int* __restrict__ toff, const int* __restrict__ ttok,
                                                                   const int* __restrict__ tnxt, int n_nodes, int* __restrict__ node,
                                                                   int* __restrict__ state, int* __restrict__ out, int max_steps, int B,
-                                                                  int eos, int pad) {
+                                                                  int eos, int pad, PickProcs pp) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const bf16_t* row = logits + (long)b * ldl;
+    const unsigned* srow = (PROC && pp.seen) ? pp.seen + (long)b * pp.seen_ld : nullptr;     // (min_new is refused with a trie)
     const int n = node[b];
     int e0 = 0, e1 = 0;
     if (n >= 0 && n < n_nodes) {
@@ -122,13 +159,15 @@ __global__ __launch_bounds__(TRIE_T) void decode_pick_trie_kernel(const bf16_t* 
     for (int e = e0 + tid; e < e1; e += TRIE_T) {
         const int v = ttok[e];
         if (v < 0 || !pick_allowed(v, V, special0, nspecial)) continue;
-        const float x = bf2f(row[v]);
+        float x = bf2f(row[v]);
+        if (PROC && proc_hit(srow, v)) x = proc_penalise(x, pp.pen);
         if (pick_beats(x, v, best, bi)) { best = x; bi = v; be = e; }
     }
     pick_reduce<TRIE_T, true>(best, bi, be);
     if (tid == 0) {
         const bool none = bi == PICK_NONE;
         const bool was = pick_emit(state, out, max_steps, B, b, none ? eos : bi, eos, pad);
+        if (PROC && !was) proc_mark(pp, b, none ? eos : bi, V);
         if (!was && !none) {
             const int m = tnxt[be];
             if (m >= 0 && m < n_nodes) node[b] = m;
@@ -204,14 +243,15 @@ __device__ __forceinline__ void samp_select_mass(const unsigned long long* mass,
     __syncthreads();
 }
 constexpr float SAMP_MASS_ONE = 1099511627776.f;                      // 2^40: the fixed-point unit of the top-p masses
-template <bool TRIE>
+template <bool TRIE, bool PROC>
 __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t* __restrict__ logits, int ldl, int V, int special0,
                                                                     int nspecial, const int* __restrict__ toff, const int* __restrict__ ttok,
                                                                     const int* __restrict__ tnxt, int n_nodes, int* __restrict__ node,
                                                                     float temperature, int top_k, float top_p,
                                                                     const uint64_t* __restrict__ rng, float* __restrict__ u_out,
                                                                     int* __restrict__ kept_out, int* __restrict__ state,
-                                                                    int* __restrict__ out, int max_steps, int B, int eos, int pad) {
+                                                                    int* __restrict__ out, int max_steps, int B, int eos, int pad,
+                                                                    PickProcs pp) {
     __shared__ int hist[2][256];
     __shared__ unsigned long long mass[2][256], s_above[2];
     __shared__ int s_bin[2], s_rank[2], s_pbin[2], s_max, s_first, s_last, s_kept;
@@ -233,6 +273,8 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
         if (tid == 0) pick_emit(state, out, max_steps, B, b, pad, eos, pad);   // written by this block's thread 0 alone)
         return;
     }
+    const unsigned* srow = (PROC && pp.seen) ? pp.seen + (long)b * pp.seen_ld : nullptr;
+    const bool ban = PROC && state[7 * B + 2] < pp.min_new;          // `eos` is no candidate yet (cnt moves in decode_advance_kernel only)
     int e0 = 0, n = V;
     if (TRIE) {
         const int nd = node[b];
@@ -247,8 +289,9 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
     // item i -> its id v and the order-preserving key of its logit (larger logit <=> larger key; -0 counts as +0), -1: no candidate
     auto key_of = [&](int i, int& v) -> int {
         v = TRIE ? ttok[e0 + i] : i;
-        if (v < 0 || !pick_allowed(v, V, special0, nspecial)) return -1;
+        if (v < 0 || !pick_allowed(v, V, special0, nspecial) || (PROC && ban && v == eos)) return -1;
         uint32_t h = row[v];
+        if (PROC && proc_hit(srow, v)) h = f2bf(proc_penalise(bf2f((bf16_t)h), pp.pen));
         if ((h & 0x7fffu) > 0x7f80u) return -1;                       // NaN
         if (h == 0x8000u) h = 0;
         return (int)((h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u));
@@ -351,6 +394,7 @@ __global__ __launch_bounds__(SAMP_T) void decode_pick_sample_kernel(const bf16_t
         const bool none = i < 0;
         if (!none) key_of(i, v);
         pick_emit(state, out, max_steps, B, b, none ? eos : v, eos, pad);
+        if (PROC) proc_mark(pp, b, none ? eos : v, V);                // (a finished row has returned above)
         const int cnt = state[7 * B + 2];
         if (kept_out && cnt >= 0 && cnt < max_steps) kept_out[(long)cnt * B + b] = none ? 0 : s_kept;
         if (TRIE && !none) {
@@ -407,43 +451,71 @@ extern "C" {
 
 int nv_decode_state_ints(int B) { return B > 0 ? 7 * B + 4 : 0; }
 
+// The one pick entry (include/navillm_hip_procs.h): greedy or sampled, over the vocabulary or over a trie node's children, with or
+// without the processors.  The four entries below are calls of it with the processors off, which launch the PROC = false kernels.
+int nv_decode_pick_proc_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
+                             const int* trie_nxt, int n_nodes, int* node, int sample, float temperature, int top_k, float top_p,
+                             const unsigned long long* rng, float* u_out, int* kept_out, unsigned* seen, int seen_ld, float rep_penalty,
+                             int min_new, int* state, int* out, int max_steps, int B, int eos, int pad, void* stream) {
+    if (!logits || !state || !out || B <= 0 || V <= 0 || ldl < V || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
+    const bool trie = trie_off || trie_tok || trie_nxt || node || n_nodes != 0;
+    if (trie && (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0)) return NV_ERR_ARG;
+    if (sample) {
+        if (!rng) return NV_ERR_ARG;
+        if (!(temperature > 0.f && temperature <= 3.402823466e38f) || top_k < 0) return NV_ERR_ARG;  // (a NaN fails both comparisons)
+        if (!(top_p > 0.f && top_p <= 1.f)) return NV_ERR_ARG;                                       // (so does this one)
+        if (top_p < 1.f && V > (1 << 23)) return NV_ERR_ARG;                                         // the 64-bit masses: V * 2^40 < 2^63
+    }
+    if (!(rep_penalty > 0.f && rep_penalty <= 3.402823466e38f) || min_new < 0) return NV_ERR_ARG;
+    if (rep_penalty != 1.f && !seen) return NV_ERR_ARG;
+    if (seen && seen_ld < (V + 31) / 32) return NV_ERR_ARG;
+    if (min_new > 0 && trie) return NV_ERR_ARG;                       // a trie leaf allows `eos` alone: the trie decides where an answer ends
+    const bool proc = seen || min_new > 0;
+    const PickProcs pp = {seen, seen_ld, rep_penalty, min_new};
+    const bf16_t* lg = (const bf16_t*)logits;
+    const uint64_t* r = (const uint64_t*)rng;
+    hipStream_t st = (hipStream_t)stream;
+#define NV_PICK_GREEDY(K, NT, ...) NV_LAUNCH(K, dim3(B), dim3(NT), 0, st, lg, ldl, V, special0, nspecial, __VA_ARGS__)
+#define NV_PICK_SAMPLE(K) \
+    NV_LAUNCH(K, dim3(B), dim3(SAMP_T), 0, st, lg, ldl, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, \
+              top_p, r, u_out, kept_out, state, out, max_steps, B, eos, pad, pp)
+    if (sample) {
+        if (trie && proc) NV_PICK_SAMPLE((decode_pick_sample_kernel<true, true>));
+        else if (trie) NV_PICK_SAMPLE((decode_pick_sample_kernel<true, false>));
+        else if (proc) NV_PICK_SAMPLE((decode_pick_sample_kernel<false, true>));
+        else NV_PICK_SAMPLE((decode_pick_sample_kernel<false, false>));
+    } else if (trie) {
+        if (proc) NV_PICK_GREEDY(decode_pick_trie_kernel<true>, TRIE_T, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out, max_steps, B, eos, pad, pp);
+        else NV_PICK_GREEDY(decode_pick_trie_kernel<false>, TRIE_T, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out, max_steps, B, eos, pad, pp);
+    } else {
+        if (proc) NV_PICK_GREEDY(decode_pick_kernel<true>, PICK_T, state, out, max_steps, B, eos, pad, pp);
+        else NV_PICK_GREEDY(decode_pick_kernel<false>, PICK_T, state, out, max_steps, B, eos, pad, pp);
+    }
+#undef NV_PICK_GREEDY
+#undef NV_PICK_SAMPLE
+    return nv_check_launch();
+}
+
 int nv_decode_pick_bf16(const void* logits, int ldl, int V, int special0, int nspecial, int* state, int* out, int max_steps, int B, int eos,
                         int pad, void* stream) {
-    if (!logits || !state || !out || B <= 0 || V <= 0 || ldl < V || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
-    NV_LAUNCH(decode_pick_kernel, dim3(B), dim3(PICK_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0, nspecial, state, out,
-              max_steps, B, eos, pad);
-    return nv_check_launch();
+    return nv_decode_pick_proc_bf16(logits, ldl, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0, 0.f, 0, 1.f, nullptr, nullptr,
+                                    nullptr, nullptr, 0, 1.0f, 0, state, out, max_steps, B, eos, pad, stream);
 }
 
 int nv_decode_pick_trie_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
                              const int* trie_nxt, int n_nodes, int* node, int* state, int* out, int max_steps, int B, int eos, int pad,
                              void* stream) {
-    if (!logits || !trie_off || !trie_tok || !trie_nxt || !node || !state || !out) return NV_ERR_ARG;
-    if (B <= 0 || V <= 0 || ldl < V || n_nodes <= 0 || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
-    NV_LAUNCH(decode_pick_trie_kernel, dim3(B), dim3(TRIE_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0, nspecial,
-              trie_off, trie_tok, trie_nxt, n_nodes, node, state, out, max_steps, B, eos, pad);
-    return nv_check_launch();
+    if (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0) return NV_ERR_ARG;
+    return nv_decode_pick_proc_bf16(logits, ldl, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0, 0.f, 0, 1.f, nullptr,
+                                    nullptr, nullptr, nullptr, 0, 1.0f, 0, state, out, max_steps, B, eos, pad, stream);
 }
 
 int nv_decode_pick_sample_topp_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,
                                     const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k, float top_p,
                                     const unsigned long long* rng, float* u_out, int* kept_out, int* state, int* out, int max_steps, int B,
                                     int eos, int pad, void* stream) {
-    if (!logits || !rng || !state || !out || B <= 0 || V <= 0 || ldl < V || max_steps < 0 || nspecial < 0) return NV_ERR_ARG;
-    if (!(temperature > 0.f && temperature <= 3.402823466e38f) || top_k < 0) return NV_ERR_ARG;      // (a NaN fails both comparisons)
-    if (!(top_p > 0.f && top_p <= 1.f)) return NV_ERR_ARG;                                           // (so does this one)
-    if (top_p < 1.f && V > (1 << 23)) return NV_ERR_ARG;                                             // the 64-bit masses: V * 2^40 < 2^63
-    const bool trie = trie_off || trie_tok || trie_nxt || node || n_nodes != 0;
-    if (trie && (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0)) return NV_ERR_ARG;
-    if (trie)
-        NV_LAUNCH(decode_pick_sample_kernel<true>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
-                  nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, top_p, (const uint64_t*)rng, u_out, kept_out,
-                  state, out, max_steps, B, eos, pad);
-    else
-        NV_LAUNCH(decode_pick_sample_kernel<false>, dim3(B), dim3(SAMP_T), 0, (hipStream_t)stream, (const bf16_t*)logits, ldl, V, special0,
-                  nspecial, nullptr, nullptr, nullptr, 0, nullptr, temperature, top_k, top_p, (const uint64_t*)rng, u_out, kept_out, state,
-                  out, max_steps, B, eos, pad);
-    return nv_check_launch();
+    return nv_decode_pick_proc_bf16(logits, ldl, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 1, temperature, top_k, top_p,
+                                    rng, u_out, kept_out, nullptr, 0, 1.0f, 0, state, out, max_steps, B, eos, pad, stream);
 }
 
 int nv_decode_pick_sample_bf16(const void* logits, int ldl, int V, int special0, int nspecial, const int* trie_off, const int* trie_tok,

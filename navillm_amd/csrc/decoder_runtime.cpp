@@ -20,6 +20,7 @@
 
 #include "../../include/navillm_hip.h"
 #include "../../include/navillm_hip_topp.h"
+#include "../../include/navillm_hip_procs.h"
 
 namespace {
 
@@ -321,12 +322,15 @@ int nv_decoder_extend(const nv_decoder* p, const void* x_in, const int* pos, con
 // nv_decoder_trie_step is the same step with the argmax taken over the children of each sample's trie node (node [B], moved along
 // the picked edge); nv_decoder_sample_step draws the token instead (nv_decode_pick_sample_bf16: temperature, top-k, one Philox draw
 // per row keyed by the device words rng = {seed, offset}), over the vocabulary or over the node's children, and
-// nv_decoder_sample_topp_step adds the top-p warper (nv_decode_pick_sample_topp_bf16; top_p = 1 is nv_decoder_sample_step).  All four
-// are decode_step() below: `node == nullptr` selects the unconstrained candidates, `rng == nullptr` the argmax.
+// nv_decoder_sample_topp_step adds the top-p warper (nv_decode_pick_sample_topp_bf16; top_p = 1 is nv_decoder_sample_step), and
+// nv_decoder_proc_step (include/navillm_hip_procs.h) the repetition penalty and the minimum length.  All five are decode_step() below,
+// whose pick is nv_decode_pick_proc_bf16: `node == nullptr` selects the unconstrained candidates, `sample == 0` the argmax,
+// `seen == nullptr` with min_new = 0 the pick without processors.
 static int decode_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
-                       const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, float temperature, int top_k,
-                       float top_p, const unsigned long long* rng, void* logits, void* x, int* state, int* out, int max_steps, const int* kv0,
-                       void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
+                       const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, int sample, float temperature,
+                       int top_k, float top_p, const unsigned long long* rng, unsigned* seen, int seen_ld, float rep_penalty, int min_new,
+                       void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap,
+                       int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !hs || !embed || !lm_head || !logits || !x || !state || !out || !kv0 || !attn_buf || !lse || !workspace) return NV_ERR_ARG;
     if (B <= 0 || Vp < V || V <= 0) return NV_ERR_ARG;
     const int d = p->d;
@@ -334,11 +338,8 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
     if (B <= 16 && (d & 31) == 0) rc = nv_gemv_bf16(hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, stream);
     else rc = nv_gemm_bf16_ws(0, hs, lm_head, logits, nullptr, B, Vp, d, d, d, Vp, Vp, 0, 0, p->gemm_ws, stream);
     if (rc != NV_OK) return rc;
-    if (rng) rc = nv_decode_pick_sample_topp_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature,
-                                                  top_k, top_p, rng, nullptr, nullptr, state, out, max_steps, B, eos, pad, stream);
-    else if (node) rc = nv_decode_pick_trie_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, state, out,
-                                            max_steps, B, eos, pad, stream);
-    else rc = nv_decode_pick_bf16(logits, Vp, V, special0, nspecial, state, out, max_steps, B, eos, pad, stream);
+    rc = nv_decode_pick_proc_bf16(logits, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, sample, temperature, top_k, top_p,
+                                  rng, nullptr, nullptr, seen, seen_ld, rep_penalty, min_new, state, out, max_steps, B, eos, pad, stream);
     if (rc != NV_OK) return rc;
     if ((rc = nv_decode_advance(state, B, cap, stream)) != NV_OK) return rc;
     int* tok = state;
@@ -350,8 +351,8 @@ static int decode_step(const nv_decoder* p, void* hs, const void* embed, const v
 int nv_decoder_greedy_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
                            void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B,
                            int cap, int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, 1.f, nullptr, logits, x, state,
-                       out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, nullptr, nullptr, nullptr, 0, nullptr, 0, 0.f, 0, 1.f, nullptr, nullptr, 0,
+                       1.f, 0, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
 int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
@@ -359,8 +360,8 @@ int nv_decoder_trie_step(const nv_decoder* p, void* hs, const void* embed, const
                          int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!trie_off || !trie_tok || !trie_nxt || !node || n_nodes <= 0) return NV_ERR_ARG;
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0.f, 0, 1.f, nullptr, logits, x,
-                       state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 0, 0.f, 0, 1.f, nullptr, nullptr,
+                       0, 1.f, 0, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
 }
 
 int nv_decoder_sample_topp_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
@@ -369,8 +370,23 @@ int nv_decoder_sample_topp_step(const nv_decoder* p, void* hs, const void* embed
                                 int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap, int eos, int pad, void* workspace,
                                 size_t workspace_bytes, void* stream) {
     if (!rng) return NV_ERR_ARG;                  // (the trie arguments, temperature, top_k and top_p are checked by the pick)
-    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, temperature, top_k, top_p,
-                       rng, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes, stream);
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, 1, temperature, top_k, top_p,
+                       rng, nullptr, 0, 1.f, 0, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad, workspace, workspace_bytes,
+                       stream);
+}
+
+int nv_decoder_proc_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,
+                         const int* trie_off, const int* trie_tok, const int* trie_nxt, int n_nodes, int* node, int sample, float temperature,
+                         int top_k, float top_p, const unsigned long long* rng, unsigned* seen, int seen_ld, float rep_penalty, int min_new,
+                         void* logits, void* x, int* state, int* out, int max_steps, const int* kv0, void* attn_buf, float* lse, int B, int cap,
+                         int eos, int pad, void* workspace, size_t workspace_bytes, void* stream) {
+    // what the pick would refuse about the processors is refused here, in front of the lm_head launch
+    if (!(rep_penalty > 0.f && rep_penalty <= 3.402823466e38f) || min_new < 0 || (rep_penalty != 1.f && !seen)) return NV_ERR_ARG;
+    if ((seen && seen_ld < (V + 31) / 32) || (min_new > 0 && (trie_off || trie_tok || trie_nxt || node || n_nodes != 0))) return NV_ERR_ARG;
+    if (sample && !rng) return NV_ERR_ARG;
+    return decode_step(p, hs, embed, lm_head, Vp, V, special0, nspecial, trie_off, trie_tok, trie_nxt, n_nodes, node, sample, temperature, top_k,
+                       top_p, rng, seen, seen_ld, rep_penalty, min_new, logits, x, state, out, max_steps, kv0, attn_buf, lse, B, cap, eos, pad,
+                       workspace, workspace_bytes, stream);
 }
 
 int nv_decoder_sample_step(const nv_decoder* p, void* hs, const void* embed, const void* lm_head, int Vp, int V, int special0, int nspecial,

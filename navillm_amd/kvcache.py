@@ -88,6 +88,56 @@ def _top_p_warp(lg, top_p):
     return lg.masked_fill(torch.zeros_like(drop).scatter(1, order, drop), float("-inf"))
 
 
+def _check_processors(repetition_penalty, min_new_tokens, trie):
+    """the arguments of the two logits processors as generate() takes them -> (p32, min_new), or None when both are off.  p32 is the
+    penalty as the fp32 every implementation of the rule multiplies and divides by (DESIGN.md §4 "Logits processors"); off is p32 == 1
+    with min_new == 0.  Raises ValueError for anything but None or a finite real > 0 (as an fp32 too) / None or an int >= 0, bools
+    excluded, and for a minimum length under a trie."""
+    p = 1.0 if repetition_penalty is None else repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0.0 < float(p) < math.inf:           # (a NaN fails the comparison)
+        raise ValueError(f"KVCacheLM.generate: repetition_penalty must be None or a finite real number > 0, not {repetition_penalty!r}")
+    with np.errstate(over="ignore", under="ignore"):
+        p32 = float(np.float32(p))
+    if not 0.0 < p32 < math.inf:
+        raise ValueError(f"KVCacheLM.generate: repetition_penalty {repetition_penalty!r} is not a finite number > 0 in fp32")
+    n = 0 if min_new_tokens is None else min_new_tokens
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+        raise ValueError(f"KVCacheLM.generate: min_new_tokens must be None or an int >= 0, not {min_new_tokens!r}")
+    n = min(int(n), 2 ** 31 - 1)
+    if n > 0 and trie is not None:
+        raise ValueError("KVCacheLM.generate: min_new_tokens > 0 cannot be combined with a trie (a trie leaf allows eos alone: the trie "
+                         "decides where an answer ends)")
+    return None if (p32 == 1.0 and n == 0) else (p32, n)
+
+
+def _seen_bitmap(seqs, V):
+    """the kernel's `seen` bitmap of the prompts: [B, ceil(V / 32)] uint32, bit v & 31 of word v >> 5 of row b set for every id v of
+    seqs[b] inside [0, V)"""
+    bm = np.zeros((len(seqs), (V + 31) // 32), np.uint32)
+    for b, x in enumerate(seqs):
+        ids = np.unique(np.asarray(x, dtype=np.int64))
+        ids = ids[(ids >= 0) & (ids < V)]
+        np.bitwise_or.at(bm[b], ids >> 5, np.uint32(1) << (ids & 31).astype(np.uint32))
+    return bm
+
+
+def _penalise_seen(lg, seen, p32):
+    """the repetition penalty on fp32 logits [B, V] that hold bf16 values, in place: the entries of row b at the ids of seen[b] become
+    bf16(x * p32) when x < 0, else bf16(x / p32), widened again.  Computed on the CPU on the few seen entries alone: torch's CPU fp32
+    divide is the correctly rounded one of the rule (a GPU divide by a scalar may multiply by the reciprocal instead)."""
+    V = lg.shape[1]
+    rows = np.concatenate([np.full(len(s), b, np.int64) for b, s in enumerate(seen)])
+    cols = np.concatenate([np.fromiter(s, np.int64, len(s)) for s in seen])
+    ok = (cols >= 0) & (cols < V)
+    if not ok.any():
+        return lg
+    idx = ops.h2d(torch.from_numpy(np.stack([rows[ok], cols[ok]])), lg.device)
+    x = lg[idx[0], idx[1]].cpu()
+    x = torch.where(x < 0, x * p32, x / p32).to(BF16).float()
+    lg[idx[0], idx[1]] = ops.h2d(x, lg.device)
+    return lg
+
+
 class KVCacheLM:
     def __init__(self, model, batch_size, capacity=1024):
         cfg = model.cfg
@@ -270,7 +320,7 @@ class KVCacheLM:
 
     @torch.no_grad()
     def generate(self, ids_list, vis_idx_list=None, vis_all=None, max_new_tokens=50, eos_token_id=2, pad_token_id=0,
-                 trie=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0):
+                 trie=None, do_sample=False, temperature=1.0, top_k=50, top_p=1.0, repetition_penalty=1.0, min_new_tokens=0):
         """Greedy decoding with HF's bookkeeping (`generate(do_sample=False)`): finished rows emit `pad_token_id`, the
         loop ends when every row has produced `eos_token_id` or after `max_new_tokens`.  `trie` (tools/trie.py protocol:
         `.root`, `.get_child_index(node)`, `.get_next_node(node, w)`) constrains each step like TrieLogitsProcessor.
@@ -285,7 +335,13 @@ class KVCacheLM:
         room in the cache, an eligible trie; anything else keeps the host loop): the same distribution, drawn by
         `decode_pick_sample_kernel` from Philox counters taken from torch's CUDA generator (`torch.manual_seed` makes a run
         reproducible); `last_sample` then records the seed, the offset, temperature and top_k, and top_p when the warper is on.
+        repetition_penalty (None or 1.0: off; else a finite real > 0) and min_new_tokens (None or 0: off; else an int > 0, not with a
+        trie) are HF's RepetitionPenaltyLogitsProcessor and MinNewTokensLengthLogitsProcessor by the rule of DESIGN.md §4 "Logits
+        processors", after the special-id mask and in front of the trie and the warpers, in every kind of decoding and on both loops;
+        anything else raises ValueError.  With one of them on, `last_generate` gains "processors"; with both off the call is the call
+        without them.
         Returns B lists with the new tokens only."""
+        procs = _check_processors(repetition_penalty, min_new_tokens, trie)          # (checked before any work, whichever loop will run)
         if do_sample:                                              # (checked before any work, whichever loop will run)
             if top_p is None:
                 top_p = 1.0
@@ -298,6 +354,9 @@ class KVCacheLM:
         vix = None if vis_idx_list is None else [list(v) for v in vis_idx_list]
         keys = None if vis_all is None else [("gen", r) for r in range(vis_all.shape[0])]   # constant within one call
         self.last_generate = {"loop": "host", "trie": trie is not None}
+        if procs is not None:
+            self.last_generate["processors"] = {"repetition_penalty": float(1.0 if repetition_penalty is None else repetition_penalty),
+                                                "min_new_tokens": procs[1]}
         self.last_sample = None
         if do_sample:
             on_device = (DEVICE_SAMPLE and isinstance(temperature, (int, float)) and math.isfinite(temperature)
@@ -315,13 +374,18 @@ class KVCacheLM:
                     sampler = {"seed": int(seed), "offset": int(offset), "temperature": float(temperature),
                                "top_k": min(int(top_k or 0), 2 ** 31 - 1), "top_p": top_p}
                     self.last_sample = {k: v for k, v in sampler.items() if k != "top_p" or top_p < 1.0}
-                return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables, sampler)
+                return self._generate_on_device(seqs, vix, vis_all, keys, max_new_tokens, eos_token_id, pad_token_id, tables, sampler, procs)
         out = [[] for _ in range(B)]
         unfinished = [True] * B
+        seen = None if procs is None or procs[0] == 1.0 else [set(x) for x in seqs]      # each row's own ids: no padding is ever part of a row
         nodes = [trie.root for _ in range(B)] if trie is not None else None
         for step in range(max_new_tokens):
             Hs = self.extend(seqs, vix, vis_all, keys)
             lg = self.logits_last(Hs)
+            if seen is not None:
+                lg = _penalise_seen(lg, seen, procs[0])
+            if procs is not None and step < procs[1] and 0 <= eos_token_id < lg.shape[1]:
+                lg[:, eos_token_id] = float("-inf")
             if trie is not None:
                 if step > 0:
                     nodes = [trie.get_next_node(nodes[b], seqs[b][-1]) for b in range(B)]
@@ -346,6 +410,8 @@ class KVCacheLM:
                 seqs[b].append(t)
                 if vix is not None:
                     vix[b].append(-1)
+                if seen is not None and unfinished[b]:
+                    seen[b].add(t)                             # (a finished row's `pad` marks nothing)
                 if unfinished[b] and t == eos_token_id:
                     unfinished[b] = False
             if not any(unfinished):
@@ -391,15 +457,18 @@ class KVCacheLM:
              "rng": torch.zeros((2,), dtype=torch.int64, device=dev),   # {seed, offset} of the sampled pick: changes per call, so not a launch argument
              "state": torch.zeros((n,), dtype=I32, device=dev), "hs": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev),
              "x": torch.zeros((B, cfg.hidden_size), dtype=BF16, device=dev), "logits": torch.zeros((B, vp), dtype=BF16, device=dev),
+             "seen": torch.zeros((B, (cfg.vocab_size + 31) // 32), dtype=I32, device=dev),   # each row's seen-id bitmap (the processors only)
              "fin_host": [torch.zeros((B,), dtype=I32).pin_memory() for _ in range(3)]}     # landing buffers of the lagging `fin` poll
         g["out"] = torch.zeros((g["max_steps"], B), dtype=I32, device=dev)
         self._greedy = g
         return g
 
-    def _greedy_step(self, g, eos, pad, stream, dec, trie=None, sampler=None):
+    def _greedy_step(self, g, eos, pad, stream, dec, trie=None, sampler=None, procs=None):
         """`dec`: the native decoder, resolved by the caller BEFORE any stream capture (nothing here may allocate or rebuild);
         `trie`: the device tables of `_trie_tables` -> the step picks among the children of g["node"];
-        `sampler`: temperature, top_k and top_p -> the step draws its token, keyed by the two words in g["rng"]"""
+        `sampler`: temperature, top_k and top_p -> the step draws its token, keyed by the two words in g["rng"];
+        `procs`: (p32, min_new) of `_check_processors` -> nv_decoder_proc_step, the same step with the processors over g["seen"];
+        None takes the symbols the call took before there were processors"""
         m, cfg, st = self.model, self.model.cfg, self.model.store
         sp = cfg.special_token_ids
         head = (dec, g["hs"].data_ptr(), st.p("lang_model.model.embed_tokens.weight").data_ptr(), st.lm_head_padded().data_ptr(), st.vocab_pad,
@@ -408,7 +477,14 @@ class KVCacheLM:
                 self.attn.data_ptr(), self.lse.data_ptr(), self.B, self.cap, eos, pad, self._ws.data_ptr(), self._ws.numel(), stream)
         tr = (None, None, None, 0, None) if trie is None else (trie["off"].data_ptr(), trie["tok"].data_ptr(), trie["nxt"].data_ptr(),
                                                                trie["n_nodes"], g["node"].data_ptr())
-        if sampler is not None:
+        if procs is not None:
+            smp = (0, 0.0, 0, 1.0, None)
+            if sampler is not None:
+                smp = (1, sampler["temperature"], sampler["top_k"], min(max(float(np.float32(sampler["top_p"])), float(np.finfo(np.float32).tiny)), 1.0),
+                       g["rng"].data_ptr())
+            _lib.check(ops._L().nv_decoder_proc_step(*head, *tr, *smp, g["seen"].data_ptr(), g["seen"].shape[1], procs[0], procs[1], *tail),
+                       "nv_decoder_proc_step")
+        elif sampler is not None:
             # what the kernel is handed is an fp32: a top_p that rounds to 1 is off, one that rounds to 0 keeps the maximum alone either way
             p32 = max(float(np.float32(sampler["top_p"])), float(np.finfo(np.float32).tiny))
             if p32 < 1.0:
@@ -423,11 +499,12 @@ class KVCacheLM:
             _lib.check(ops._L().nv_decoder_trie_step(*head, *tr, *tail), "nv_decoder_trie_step")
 
     @torch.no_grad()
-    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad, trie=None, sampler=None):
+    def _generate_on_device(self, seqs, vix, vis_all, keys, max_new_tokens, eos, pad, trie=None, sampler=None, procs=None):
         """prefill through `extend` (host-built indices, once), then max_new_tokens replays of ONE captured step
         (nv_decoder_greedy_step: lm_head -> masked argmax + finished/pad bookkeeping -> cache indices -> embedding -> decoder layers;
         with `trie`, the device tables of `_trie_tables`: nv_decoder_trie_step, the argmax over the children of each row's trie node;
-        with `sampler`: nv_decoder_sample_step / nv_decoder_sample_topp_step, a draw among the same candidates).
+        with `sampler`: nv_decoder_sample_step / nv_decoder_sample_topp_step, a draw among the same candidates;
+        with `procs`: nv_decoder_proc_step, any of these with the repetition penalty and the minimum length).
         The host never waits for a token: it polls the `fin` flags two steps behind and trims the output where HF would have stopped."""
         B, dev = self.B, self.model.device
         g = self._greedy_state(max_new_tokens)
@@ -439,19 +516,29 @@ class KVCacheLM:
         kind = trie is not None                                # which captured graph: free / trie, and ("sample", free / trie)
         if sampler is not None:
             kind = ("sample", kind)
+        if procs is not None:                                  # processor-on graphs are kinds of their own: the plain ones stay captured
+            kind = ("proc", kind)
         if USE_HIP_GRAPH and kind not in g["graphs"]:
             # one eager step on a scratch state BEFORE the prefill: the kernels' first-use initialisation (hipFuncSetAttribute, device
             # queries) must not happen inside a stream capture.  It writes cache row 0 of every sample, which the prefill rewrites.
             g["state"].zero_()
             if trie is not None:
                 g["node"].zero_()
-            self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler)
+            if procs is not None:
+                g["seen"].zero_()                              # the scratch step marks what it emits; the upload below resets every word
+            self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler, procs)
         Hs = self.extend(seqs, vix, vis_all, keys)
         assert self._decoder() is dec, "the decoder table changed between prefill and decode"
         n = g["state"].numel()
         init = np.zeros(n, np.int32)
         init[2 * B:3 * B] = [len(x) for x in seqs]
-        g["state"].copy_(ops.h2d(torch.from_numpy(init), dev))
+        if procs is None:
+            g["state"].copy_(ops.h2d(torch.from_numpy(init), dev))
+        else:                                                  # the prompts' bitmap rides on the same H2D copy
+            bm = _seen_bitmap(seqs, self.model.cfg.vocab_size) if procs[0] != 1.0 else np.zeros(tuple(g["seen"].shape), np.uint32)
+            up = ops.h2d(torch.from_numpy(np.concatenate([init, bm.view(np.int32).reshape(-1)])), dev)
+            g["state"].copy_(up[:n])
+            g["seen"].copy_(up[n:].view(g["seen"].shape))
         g["hs"].copy_(Hs)
         key = (self._dec_key, self._ws.data_ptr(), eos, pad, g["out"].data_ptr())
         if trie is not None:                                   # the tables' addresses and the node count are frozen launch arguments too
@@ -461,12 +548,14 @@ class KVCacheLM:
             key += (sampler["temperature"], sampler["top_k"], sampler["top_p"], g["rng"].data_ptr())
             words = np.array([sampler["seed"], sampler["offset"]], dtype=np.uint64).view(np.int64)
             g["rng"].copy_(ops.h2d(torch.from_numpy(words), dev))
+        if procs is not None:                                  # and the processors' two settings and the bitmap's address
+            key += (procs[0], procs[1], g["seen"].data_ptr())
         if USE_HIP_GRAPH and g["graphs"].get(kind, (None, None))[0] != key:
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream())
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph, stream=side):
-                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec, trie, sampler)
+                self._greedy_step(g, eos, pad, torch.cuda.current_stream().cuda_stream, dec, trie, sampler, procs)
             g["graphs"][kind] = (key, graph)                   # capture enqueues nothing: the first replay is step 0
         events = []
         steps = 0
@@ -474,7 +563,7 @@ class KVCacheLM:
             if USE_HIP_GRAPH:
                 g["graphs"][kind][1].replay()
             else:
-                self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler)
+                self._greedy_step(g, eos, pad, ops._st(), dec, trie, sampler, procs)
             steps += 1
             if len(events) >= 2:                               # flags as of two steps ago: the host stays ahead of the GPU
                 ev, snap = events.pop(0)

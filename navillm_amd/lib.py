@@ -1,7 +1,7 @@
 """ctypes binding of libnavillm_hip.so -- the ONLY way the package reaches the GPU kernels.
 
 There is no fallback: if the library is missing or a symbol declared in include/navillm_hip.h or
-include/navillm_hip_topp.h / include/navillm_hip_optim.h is not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
+include/navillm_hip_topp.h / include/navillm_hip_optim.h / include/navillm_hip_procs.h is not exported, importing/using the product path raises.  (The CPU oracle lives in oracle/ and is
 never imported from here.)
 """
 import ctypes as C
@@ -154,6 +154,13 @@ OPTIM_SIGNATURES = {
     "nv_adamw_sr": (i, [vp, vp, vp, vp, l, l, _ull, _d, _d, _d, _d, _d, i, fp, i, vp]),
 }
 
+# the same for include/navillm_hip_procs.h (the pick and the decode step with HF's repetition penalty and minimum length)
+PROC_SIGNATURES = {
+    "nv_decode_pick_proc_bf16": (i, [vp, i, i, i, i, ip, ip, ip, i, ip, i, f, i, f, vp, fp, ip, vp, i, f, i, ip, ip, i, i, i, i, vp]),
+    "nv_decoder_proc_step": (i, [vp, vp, vp, vp, i, i, i, i, ip, ip, ip, i, ip, i, f, i, f, vp, vp, i, f, i, vp, vp, ip, ip, i, ip, vp, fp, i, i, i, i,
+                                 vp, sz, vp]),
+}
+
 _lib = None
 
 
@@ -176,7 +183,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m navillm_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU/PyTorch fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **TOPP_SIGNATURES, **OPTIM_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **TOPP_SIGNATURES, **OPTIM_SIGNATURES, **PROC_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

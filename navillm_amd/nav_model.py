@@ -786,9 +786,10 @@ class NavModel(nn.Module):
 
     @torch.no_grad()
     def _generate(self, ids_cpu, am_cpu, cand_vis, hist_vis, max_new_tokens=20, trie=None, do_sample=False, temperature=1.0,
-                  top_k=50, top_p=1.0, **unused):
+                  top_k=50, top_p=1.0, repetition_penalty=1.0, min_new_tokens=0, **unused):
         """`self.lang_model.generate(...)` of nav_model.py:324-341,388-402: eos-terminated, pad = unk, special ids masked,
-        optional trie; greedy, or HF's sampling when the caller forwards `do_sample` / `temperature` / `top_k` / `top_p` (llava.py:58-62); served by
+        optional trie; greedy, or HF's sampling when the caller forwards `do_sample` / `temperature` / `top_k` / `top_p` (llava.py:58-62);
+        `repetition_penalty` and `min_new_tokens` as HF's logits processors (DESIGN.md §4 "Logits processors"); served by
         the K/V-cache decoder (navillm_amd/kvcache.py)."""
         from .kvcache import KVCacheLM
         B, S = ids_cpu.shape
@@ -804,7 +805,7 @@ class NavModel(nn.Module):
         pad = getattr(tok, "unk_token_id", None)
         gen = kv.generate(ids_l, vix_l, vis_all, max_new_tokens=max_new_tokens, eos_token_id=2 if eos is None else eos,
                           pad_token_id=0 if pad is None else pad, trie=trie, do_sample=do_sample, temperature=temperature, top_k=top_k,
-                          top_p=top_p)
+                          top_p=top_p, repetition_penalty=repetition_penalty, min_new_tokens=min_new_tokens)
         kv.reset()
         out = {"generated_ids": gen}
         if hasattr(tok, "batch_decode"):

@@ -7,7 +7,9 @@ the last one is reported, with the spread over all but the first); --free with -
 --sample [--temperature=T --top-k=K --top-p=P] (defaults 0.01, 50 and none: the reference's evaluation scripts run --do_sample
 --temperature 0.01): generate(do_sample=True) instead, host loop (torch topk / softmax / multinomial per token) vs the device loop of
 NAVILLM_DEVICE_SAMPLE; --top-p adds the nucleus warper to both (without it the call carries no top_p at all); combines with --trie,
---small and --free."""
+--small and --free.
+--rep-penalty=P and --min-new=N: generate(repetition_penalty=P, min_new_tokens=N) in every loop measured (--min-new not with --trie);
+without them the call carries neither keyword."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from navillm_amd import config as nvcfg
@@ -69,6 +71,11 @@ if "--sample" in sys.argv:
     sample = dict(do_sample=True, temperature=float(opt("temperature", 0.01)), top_k=int(opt("top-k", 50)))
     if opt("top-p", None) is not None:
         sample["top_p"] = float(opt("top-p", None))
+procs = {}
+if opt("rep-penalty", None) is not None:
+    procs["repetition_penalty"] = float(opt("rep-penalty", None))
+if opt("min-new", None) is not None:
+    procs["min_new_tokens"] = int(opt("min-new", None))
 trie, eos = None, -1
 if any(a == "--trie" or a.startswith("--trie=") for a in sys.argv):
     n_words, depth = (int(x) for x in opt("trie", "2000,24").split(","))
@@ -80,7 +87,7 @@ kv = KVCacheLM(model, B, capacity=1024)
 kv.extend([list(x) for x in ids]); torch.cuda.synchronize()
 t0 = time.perf_counter(); kv.reset(); kv.extend([list(x) for x in ids]); torch.cuda.synchronize(); tp = time.perf_counter() - t0
 name = "gpt2-small-shaped" if small else "13b" if "--13b" in sys.argv else "7b"
-print(f"{name}{' fp8' if '--fp8' in sys.argv else ''}{' trie' if trie is not None else ''}{f' sampled {sample}' if sample else ''}: prefill {B}x~{L}: {tp*1e3:.1f} ms")
+print(f"{name}{' fp8' if '--fp8' in sys.argv else ''}{' trie' if trie is not None else ''}{f' sampled {sample}' if sample else ''}{f' {procs}' if procs else ''}: prefill {B}x~{L}: {tp*1e3:.1f} ms")
 
 
 def measure(trie, eos, N):
@@ -90,7 +97,7 @@ def measure(trie, eos, N):
         pers = []
         for rep in range(reps):
             torch.cuda.synchronize(); t0 = time.perf_counter()
-            kw = dict(sample or {}, **({} if trie is None else {"trie": trie}))
+            kw = dict(sample or {}, **procs, **({} if trie is None else {"trie": trie}))
             out = kv.generate(ids, max_new_tokens=N, eos_token_id=eos, pad_token_id=0, **kw)
             torch.cuda.synchronize(); dt = time.perf_counter() - t0
             pers.append((dt - tp) / len(out[0]))
